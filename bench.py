@@ -13,7 +13,9 @@ the ranks then pull sub-batches of the job's reads (BASELINE.json configs[3]: 20
 2.5 M per GPU) from one shared cursor -- the analogue of the reference's workers pulling read blocks
 from one queue (threads.c:548) -- with no data-path collective (weak scaling: the job grows with N).
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).  A plain run sets up, warms up, times --steps steps and
+prints the line; --full adds what is measured beside the headline (host-buffer rate, CPU-reference baseline, the paired
+two-mapper step); --dump-outputs DIR writes what the timed path returned in its last step as .npy files (OutputDump).
 """
 import argparse
 import json
@@ -48,7 +50,7 @@ def parse_args():
     ap.add_argument("--sub-batch", type=int, default=262144)
     ap.add_argument("--streams", type=int, default=1, help="mappers (HIP streams) that take the sub-batches in turn: kernels of consecutive sub-batches overlap")
     ap.add_argument("--paired", action="store_true", help="BASELINE configs[2]: 1 M read PAIRS (2 x read-len, FR, fragments N(300,30), -i 500) through smaltgpu_map_pairs_resident: "
-                    "rmapPair's rounds on the GPU, the decisions between them in the library; pairs/s with kernel ms per round, roofline and cpu_baseline")
+                    "rmapPair's rounds on the GPU, the decisions between them in the library; pairs/s with kernel ms per round and roofline (cpu_baseline with --full)")
     ap.add_argument("--long", action="store_true", help="BASELINE configs[4] shape: PacBio-shape reads of 8 kbp (3 %% substitutions, 5 %% insertions, 4 %% deletions) vs the 3 Gbp "
                     "reference, k=20 s=13; --reads of them (default 3000 of the config's 100 k: a step must finish within minutes)")
     ap.add_argument("--static-shards", action="store_true", help="N > 1: contiguous shard per rank instead of the shared sub-batch cursor")
@@ -56,7 +58,81 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-buffers", action="store_true", help="skip the extra PCIe-inclusive measurement of smaltgpu_map_batch on pageable host buffers")
     ap.add_argument("--cpu-sample", type=int, default=150000)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline figure: the PCIe-inclusive host-buffer rate, the CPU-reference "
+                    "baseline and, with --paired, the extra step on two mappers (--no-cpu-baseline / --no-host-buffers leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the timed path handed back in its last step as DIR/<name>.npy "
+                    "(float32/float64; a fixed seeded sample of at most %d reads)" % DUMP_READS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs measures one GPU (the ranks of N > 1 take their sub-batches in no fixed order)")
+    return args
+
+
+DUMP_READS = 65536                 # reads of the last step whose outputs --dump-outputs writes
+DUMP_BYTES_MAX = 64 << 20
+DUMP_PAIRS = 2_000_000             # --paired: pairs whose smaltgpu_pair_info it writes (24 bytes each)
+
+
+class OutputDump:
+    """--dump-outputs: what the caller of the timed path received in the last timed step (smaltgpu_fetch_end / smaltgpu_fetch_results:
+    per read the ReadStat and the alignments with their DiffStr bytes) for a fixed, seeded sample of the step's reads.  `take` runs
+    inside the last timed step (the library reuses its result buffers for the next batch) and copies only the sampled rows."""
+    RES_COLS = ("swatscor", "q_start", "q_end", "s_start", "s_end", "sidx", "reverse", "strlen")    # not stroffs: a place in the library's buffer
+
+    def __init__(self, nreads, seed=20261016):
+        n = min(DUMP_READS, nreads)
+        self.pick = np.arange(nreads) if n == nreads else np.sort(np.random.default_rng(seed).choice(nreads, n, replace=False))
+        self.parts = []
+
+    @staticmethod
+    def _ranges(start, count):
+        """concatenation of arange(start[i], start[i] + count[i])"""
+        count = count.astype(np.int64)
+        return np.repeat(start.astype(np.int64), count) + (np.arange(int(count.sum())) - np.repeat(np.cumsum(count) - count, count))
+
+    @staticmethod
+    def _structs(ptr, ctype, n):
+        """n ctypes structures at ptr as a numpy record array (a view)"""
+        import ctypes as C
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * C.sizeof(ctype),)).view(np.dtype(ctype))
+
+    def take(self, out, first, n):
+        """out = the BatchOut of reads first .. first + n - 1 of the step"""
+        from smalt_amd import api
+        lo, hi = np.searchsorted(self.pick, [first, first + n])
+        if lo == hi:
+            return
+        loc = self.pick[lo:hi] - first
+        off = np.ctypeslib.as_array(out.res_off, shape=(n + 1,))
+        stat = self._structs(out.stat, api.ReadStat, n)[loc]
+        cnt = (off[loc + 1] - off[loc]).astype(np.int64)
+        res = self._structs(out.res, api.Result, int(off[n]))[self._ranges(off[loc], cnt)] if off[n] else None
+        if res is not None and len(res):
+            slen = res["strlen"].astype(np.int64)
+            ds = np.ctypeslib.as_array(out.diffstr, shape=(int((res["stroffs"] + slen).max()),))[self._ranges(res["stroffs"], slen)]
+            res = np.stack([res[f].astype(np.float64) for f in self.RES_COLS], axis=1)
+        else:
+            ds, res = np.zeros(0, dtype=np.uint8), np.zeros((0, len(self.RES_COLS)))
+        self.parts.append((self.pick[lo:hi], np.stack([stat[f].astype(np.float64) for f in stat.dtype.names], axis=1), cnt, res, ds.copy()))
+
+    def write(self, path):
+        """DIR/read_index.npy (the sampled reads of the step), read_stat.npy (their ReadStat fields), read_nres.npy (alignments per read),
+        results.npy (the alignments in read order, RES_COLS), diffstr.npy (their DiffStr bytes, one after the other); float64 but for the
+        bytes (float32).  Keeps the longest prefix of the sample within DUMP_BYTES_MAX; returns the number of reads written."""
+        empty = (np.zeros(0, dtype=np.int64), np.zeros((0, 10)), np.zeros(0, dtype=np.int64), np.zeros((0, len(self.RES_COLS))), np.zeros(0, dtype=np.uint8))
+        pick, stat, cnt, res, ds = (np.concatenate([p[i] for p in self.parts + [empty]]) for i in range(5))
+        owner = np.repeat(np.arange(len(cnt)), cnt)
+        nbytes_read = np.bincount(owner, weights=res[:, -1], minlength=len(cnt)).astype(np.int64)
+        size = 8 * (1 + stat.shape[1] + 1) + cnt * 8 * res.shape[1] + 4 * nbytes_read
+        keep = int(np.searchsorted(np.cumsum(size), DUMP_BYTES_MAX - 4096, side="right"))
+        nr, nb = int(cnt[:keep].sum()), int(nbytes_read[:keep].sum())
+        os.makedirs(path, exist_ok=True)
+        for name, a in (("read_index", pick[:keep].astype(np.float64)), ("read_stat", stat[:keep]), ("read_nres", cnt[:keep].astype(np.float64)),
+                        ("results", res[:nr]), ("diffstr", ds[:nb].astype(np.float32))):
+            np.save(os.path.join(path, name + ".npy"), a)
+        return keep
 
 
 def spawn_ranks(args):
@@ -287,9 +363,9 @@ def paired_main(args):
     round_ms = np.zeros(4)
     lock = threading.Lock()
 
-    def one_step(collect, nstream=nstream):
+    def one_step(collect, nstream=nstream, dump=None):
         """the blocks of the job, taken in turn by `nstream` host threads with a mapper (HIP stream) each: the host work between
-        the rounds of one block runs while the device works on the other block"""
+        the rounds of one block runs while the device works on the other block; dump: block start -> copy of its pair info"""
         tot = {"both": 0, "any": 0, "next": 0, "err": None}
 
         def drive(si):
@@ -319,6 +395,8 @@ def paired_main(args):
                 rm = (C.c_double * 4)()
                 L.smaltgpu_pairs_info(handle, C.byref(npr), C.byref(info), cl, rm)
                 a = np.ctypeslib.as_array(C.cast(info, C.POINTER(C.c_uint16)), shape=(n, 3))       # flags+rounds | nali[0] | nali[1]
+                if dump is not None:
+                    dump[b0] = OutputDump._structs(info, api.PairInfo, n).copy()
                 km = (C.c_double * 80)()
                 wk = (C.c_uint64 * 160)()
                 L.smaltgpu_pairs_timers(handle, km, wk)
@@ -346,15 +424,23 @@ def paired_main(args):
         tw = time.time()
         one_step(False)
         print("[bench] warmup step %.2f s" % (time.time() - tw), file=sys.stderr, flush=True)
+    dump = {} if args.dump_outputs else None
     torch.cuda.synchronize()
     t1 = time.time()
     both = any_ = 0
-    for _ in range(args.steps):
-        b_, a_ = one_step(True)
+    for st_ in range(args.steps):
+        b_, a_ = one_step(True, dump=dump if st_ == args.steps - 1 else None)
         both += b_
         any_ += a_
     torch.cuda.synchronize()
     dt = time.time() - t1
+    if dump is not None:        # what the caller of smaltgpu_map_pairs_resident reads back per pair (smaltgpu_pairs_info) in the last step
+        pinfo = np.concatenate([dump[b] for b in sorted(dump)])
+        pick = np.arange(npairs) if npairs <= DUMP_PAIRS else np.sort(np.random.default_rng(20261016).choice(npairs, DUMP_PAIRS, replace=False))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pair_index.npy"), pick.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "pair_info.npy"),
+                np.stack([pinfo["pairflg"][pick], pinfo["rounds"][pick], pinfo["nali"][pick, 0], pinfo["nali"][pick, 1]], axis=1).astype(np.float32))
     ntim = L.smaltgpu_timers(mappers[0].h, None, None, 0)
     tn = [L.smaltgpu_timer_name(i).decode() for i in range(ntim)]
     sw = tn.index("sw_full")
@@ -392,14 +478,14 @@ def paired_main(args):
     # the same job on two mappers (HIP streams) taking the blocks in turn: the host work between the rounds of one block runs
     # while the device works on the other block.  Not `value`: kernels of two blocks share the device, so their event durations
     # are no longer those of a kernel on its own.
-    if nstream == 1:
+    if args.full and nstream == 1:
         one_step(False, 2)
         torch.cuda.synchronize()
         t2 = time.time()
         b2, _ = one_step(False, 2)
         torch.cuda.synchronize()
         line["two_streams"] = {"pairs_per_s": b2 / (time.time() - t2), "note": "blocks dealt to two mappers; one extra step, not `value`"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             line["cpu_baseline"] = cpu_baseline_pairs(args, gix, reads.cpu().numpy().reshape(npairs, rlen), mates.cpu().numpy().reshape(npairs, rlen), rlen, (cores, host_cores))
         except Exception as e:
@@ -459,7 +545,7 @@ def long_main(args):
     print("[bench] setup: reference, index (%.1f ms on the device) and %d reads of ~%d bases in %.1f s" % (gix.build_ms, nreads, rlen, setup_s), file=sys.stderr, flush=True)
     ms_acc, work_acc = {}, [0] * 32
 
-    def one_step(collect):
+    def one_step(collect, dump=None):
         mapped = 0
         for b0 in range(0, nreads, batch):
             n = min(batch, nreads - b0)
@@ -472,6 +558,8 @@ def long_main(args):
                     raise
                 out = None                 # single reads over a device-side limit keep their error code; the others are complete
             if out is not None:
+                if dump is not None:
+                    dump.take(out, b0, n)
                 st = np.ctypeslib.as_array(C.cast(out.stat, C.POINTER(C.c_uint32)), shape=(n, 10))
                 mapped += int((st[:, 7] > 0).sum())
             if collect:
@@ -485,13 +573,16 @@ def long_main(args):
         tw = time.time()
         one_step(False)
         print("[bench] warmup step %.2f s" % (time.time() - tw), file=sys.stderr, flush=True)
+    dump = OutputDump(nreads) if args.dump_outputs else None
     torch.cuda.synchronize()
     t1 = time.time()
     mapped = 0
-    for _ in range(args.steps):
-        mapped += one_step(True)
+    for st_ in range(args.steps):
+        mapped += one_step(True, dump if st_ == args.steps - 1 else None)
     torch.cuda.synchronize()
     dt = time.time() - t1
+    if dump is not None:
+        dump.write(args.dump_outputs)
     nlaunch = args.steps * ((nreads + batch - 1) // batch)
     cells = float(work_acc[2])
     sw_ms = ms_acc.get("sw_scalar", 0.0) + ms_acc.get("sw_full", 0.0)       # strips and bands run in the sw_scalar bracket
@@ -509,7 +600,7 @@ def long_main(args):
         "kernel_ms_per_step": {kk: v / args.steps for kk, v in ms_acc.items()},
         "align_phase": {"ticks_window_band_trace": work_acc[24:27], "band_passes": work_acc[27], "aligned_candidates": work_acc[28], "band_width_sum": work_acc[31]},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         smalt = os.path.join(ROOT, "oracle", "_ref", "smalt")
         cores = max(1, int(os.environ.get("SMALT_BENCH_CPU_THREADS", host_core_count())))
         try:
@@ -685,12 +776,14 @@ def main():
     ms_acc, work_acc = {}, [0] * 32
     mine = {"reads": 0, "launches": 0}
 
-    def one_step(collect, tag):
+    def one_step(collect, tag, dump=None):
         mapped = total_res = 0
 
-        def fetch(mp, n):
+        def fetch(mp, n, first):
             nonlocal mapped, total_res
             out = mp.fetch_end()
+            if dump is not None:
+                dump.take(out, first, n)
             st = np.ctypeslib.as_array(C.cast(out.stat, C.POINTER(C.c_uint32)), shape=(n, 10))
             mapped += int((st[:, 7] > 0).sum())
             total_res += int(out.res_off[n])
@@ -702,7 +795,7 @@ def main():
                     work_acc[i] += wk[i]
                 mine["reads"] += n
                 mine["launches"] += 1
-        state = {}                        # mapper -> reads of its batch in flight (kernels enqueued, results not yet fetched)
+        state = {}                        # mapper -> (reads, first read in the job) of its batch in flight (kernels enqueued, results not yet fetched)
         dealer.start(tag)
         bi = 0
         while True:
@@ -730,12 +823,12 @@ def main():
                 if prev is not None:
                     mp.fetch_begin()                      # waits for the mapper's previous sub-batch, enqueues the copies of its results
                 mp.map_batch_device(chunks[c].data_ptr() + b0 * args.read_len, 0, offs.data_ptr(), n, n * args.read_len, par)
-                state[mp] = n
+                state[mp] = (n, c * per_gpu + b0)
                 if prev is not None:
-                    fetch(mp, prev)                       # results put in read order on the host while the device runs the new sub-batch
-        for mp, n in list(state.items()):
+                    fetch(mp, *prev)                      # results put in read order on the host while the device runs the new sub-batch
+        for mp, prev in list(state.items()):
             mp.fetch_begin()
-            fetch(mp, n)
+            fetch(mp, *prev)
         return mapped, total_res
 
     def barrier():
@@ -748,14 +841,17 @@ def main():
         one_step(False, "w%d" % w)
         if rank == 0:
             print("[bench] warmup step %.2f s" % (time.time() - tw), file=sys.stderr, flush=True)
+    dump = OutputDump(per_gpu) if args.dump_outputs else None
     barrier()
     t1 = time.time()
     mapped = 0
     for st_ in range(args.steps):
-        m_, _r = one_step(True, "s%d" % st_)
+        m_, _r = one_step(True, "s%d" % st_, dump if st_ == args.steps - 1 else None)
         mapped += m_
     barrier()
     dt = time.time() - t1
+    if dump is not None:
+        dump.write(args.dump_outputs)
     if world == 1:
         mapped_all, reads_min, reads_max = mapped, mine["reads"], mine["reads"]
     else:
@@ -820,14 +916,14 @@ def main():
             "long_window_tasks_per_read": work_acc[17] / my_reads, "ranked_per_read": work_acc[3] / my_reads, "scored_in_reference_order_per_read": work_acc[4] / my_reads,
             "hits_per_read": work_acc[1] / my_reads,
         }
-        if not args.no_host_buffers:       # the boundary's host-buffer entry point: H2D of the reads + D2H of the results inside the timing
+        if args.full and not args.no_host_buffers:       # the boundary's host-buffer entry point: H2D of the reads + D2H of the results inside the timing
             hb = chunks[0][:sub * args.read_len].cpu().numpy()
             ho = (np.arange(sub + 1, dtype=np.uint64) * np.uint64(args.read_len))
             mapper.map_batch_raw(hb, ho, None, par)
             th = time.time()
             mapper.map_batch_raw(hb, ho, None, par)
             line["host_buffers"] = {"reads_per_s": sub / (time.time() - th), "reads": sub, "note": "smaltgpu_map_batch on pageable host buffers, PCIe-inclusive, one batch at a time; not `value`"}
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
             try:
                 line["cpu_baseline"] = cpu_baseline(args, None, None, None, sop, names, k, s, chunks[0].cpu().numpy(), per_gpu, args.read_len, gix)
             except Exception as e:  # the baseline is reported, never required for the GPU number

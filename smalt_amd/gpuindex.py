@@ -26,6 +26,10 @@ def make_reference_gpu(nchr: int, chrlen: int, seed: int, device, repeat_frac: f
         fams = torch.randint(0, 4, (n_fam, cons_len), dtype=torch.uint8, device=device, generator=g)
         ncopies = int(repeat_frac * chrlen / cons_len)
         ar = torch.arange(cons_len, device=device)
+        # copies overlap, and of several device writes to one base an arbitrary one lands: the copy with the highest number
+        # takes the base (max is order-free), so that the same seed gives the same reference in every run
+        copy_no = torch.arange(ncopies, dtype=torch.int32, device=device).repeat_interleave(cons_len)
+        owner = torch.empty(chrlen, dtype=torch.int32, device=device)
         for c in range(nchr):
             starts = torch.randint(0, chrlen - cons_len, (ncopies,), device=device, generator=g)
             fam = torch.randint(0, n_fam, (ncopies,), device=device, generator=g)
@@ -33,8 +37,11 @@ def make_reference_gpu(nchr: int, chrlen: int, seed: int, device, repeat_frac: f
             mut = torch.rand(copies.shape, device=device, generator=g) < divergence
             sub = torch.randint(1, 4, copies.shape, dtype=torch.uint8, device=device, generator=g)
             copies = torch.where(mut, (copies + sub) & 3, copies)
-            idx = (starts[:, None] + ar[None, :]).reshape(-1) + c * chrlen
-            ref[idx] = copies.reshape(-1)
+            idx = (starts[:, None] + ar[None, :]).reshape(-1)
+            owner.fill_(-1)
+            owner.scatter_reduce_(0, idx, copy_no, reduce="amax")
+            win = owner[idx] == copy_no
+            ref[idx[win] + c * chrlen] = copies.reshape(-1)[win]
     return ref
 
 
