@@ -398,6 +398,45 @@ int smaltgpu_report_emit(smaltgpu_report *rp, const smaltgpu_post_out *post, con
 int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pairs *pairs, const smaltgpu_reads_view *reads, const smaltgpu_reads_view *mates,
                                const char *const *seqnames, int64_t nseq, const smaltgpu_report_opts *op, const smaltgpu_pair_opts *po, int nthreads,
                                const char **text, uint64_t *len);
+/* ---- insert-size histograms: `smalt sample` and `smalt map -g <file>` (insert.c; host code, smg_inshist.cpp) -------------------
+ * `smalt sample` maps every n-th pair of a library, takes the template length of each pair whose two best alignments have a
+ * mapping quality of at least 20 (resultSetInferInsertSize, results.c:2460; smalt.c:1180-1182, :850-854) and writes the histogram
+ * of these lengths behind the SAM lines (outputHisto, smalt.c:1288-1310).  `smalt map -g` reads that file back, widens the insert
+ * range to the histogram's (smalt.c:417-426, :570) and weighs oriented, in-range pairings by the cumulative smoothed count of
+ * their template length when a pair has several pairings (assignProbabilityToPairs, resultpairs.c:782-806). */
+typedef struct smaltgpu_inshist smaltgpu_inshist;
+/* every how many pairs one is sampled: npairs / 4098, at least 1, `every` (-u) where that is smaller and above 0
+ * (insSetSamplingInterval, insert.c:192-205).  Pair i is mapped when i % interval == 0 (loadIOBuffArg, smalt.c:795-835) */
+int smaltgpu_sample_interval(uint64_t npairs, int every);
+/* histogram of a sample of n insert sizes, smoothed (insMakeHistoFromSample insert.c:330-387, insSmoothHisto :472-514, smoothGauss
+ * :253-303, calcKernelBandWidth :136-146).  SMALTGPU_EARG when the sample gives none (fewer than 2 sizes inside the binned range) */
+int smaltgpu_inshist_from_sample(smaltgpu_inshist **out, const int32_t *sample, uint64_t n);
+/* the HISTO_START ... HISTO_END section of a file, smoothed after reading; what stands ahead of the section is skipped
+ * (insReadHisto, insert.c:632-705).  SMALTGPU_EFILE: no such file, HISTO_END missing, the counts do not add up to HISTO_TOTNUM,
+ * a bin out of sequence, more bins than HISTO_BINNUM */
+int smaltgpu_inshist_read(smaltgpu_inshist **out, const char *path);
+void smaltgpu_inshist_free(smaltgpu_inshist *h);
+/* text of a histogram, owned by it and valid until the next call: the bar print of the sampled or of the smoothed counts with
+ * lines of at most `width` bars (insPrintHisto, insert.c:574-601), or the file section of the sampled counts with its title line
+ * (insWriteHisto, insert.c:603-630; width is ignored) */
+enum { SMALTGPU_HIST_SAMPLED = 0, SMALTGPU_HIST_SMOOTHED = 1, SMALTGPU_HIST_SECTION = 2 };
+int smaltgpu_inshist_text(smaltgpu_inshist *h, int what, int width, const char **text, uint64_t *len);
+/* smallest and largest insert size of the bins, their number and the number of sizes counted (insGetHistoData, insert.c:558-565);
+ * any pointer may be NULL */
+int smaltgpu_inshist_bounds(const smaltgpu_inshist *h, int32_t *lo, int32_t *hi, int32_t *nbins, uint64_t *total);
+/* count of the bin of an insert size and the sum of the counts up to and including that bin, of the smoothed (smoothed != 0) or the
+ * sampled counts; both 0 outside the bins (insGetHistoCount insert.c:531-542, insGetHistoCountCumulative :544-556); either may be NULL */
+int smaltgpu_inshist_count(const smaltgpu_inshist *h, int32_t insert_size, int smoothed, int32_t *count, int32_t *cumulative);
+/* later smaltgpu_report_emit_pairs calls on this report choose among pairings with the histogram (the ihistp argument of
+ * resultSetAddPairToReport, smalt.c:1172-1176); h = NULL detaches it.  The report does not own the histogram.  The caller widens
+ * insert_min / insert_max of the smaltgpu_pair_opts it hands to smaltgpu_map_pairs AND smaltgpu_report_emit_pairs to the
+ * histogram's bounds (updateInsertBoundariesFromSample, smalt.c:417-426) */
+int smaltgpu_report_set_inshist(smaltgpu_report *rp, const smaltgpu_inshist *h);
+/* per pair of the last smaltgpu_report_emit_pairs call on this report: the insert size `smalt sample` would add to its sample and
+ * whether there is one (resultSetInferInsertSize, results.c:2460-2483, called behind the report of the pair: smalt.c:1180-1182).
+ * The arrays belong to the report and hold until its next emit call */
+int smaltgpu_report_pair_inserts(const smaltgpu_report *rp, const int32_t **insert_size, const uint8_t **known, uint32_t *npairs);
+
 /* names and offsets of the reference sequences of an index (for the two calls above); the arrays belong to the index */
 int smaltgpu_index_seqnames(const smaltgpu_index *ix, const char *const **names, const uint64_t **sop, int64_t *nseq);
 

@@ -183,6 +183,15 @@ def lib():
         L.smaltgpu_sw_full_batch.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p,
                                              C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Params), C.POINTER(C.c_int32), C.c_int]
         L.smaltgpu_rank_sort_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.smaltgpu_sample_interval.argtypes = [C.c_uint64, C.c_int]
+        L.smaltgpu_inshist_from_sample.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_uint64]
+        L.smaltgpu_inshist_read.argtypes = [C.POINTER(C.c_void_p), C.c_char_p]
+        L.smaltgpu_inshist_free.argtypes = [C.c_void_p]
+        L.smaltgpu_inshist_text.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.smaltgpu_inshist_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        L.smaltgpu_inshist_count.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.smaltgpu_report_set_inshist.argtypes = [C.c_void_p, C.c_void_p]
+        L.smaltgpu_report_pair_inserts.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32)]
         _lib = L
     return _lib
 
@@ -194,6 +203,58 @@ def _check(rv):
 
 def device_count() -> int:
     return lib().smaltgpu_device_count()
+
+
+HIST_SAMPLED, HIST_SMOOTHED, HIST_SECTION = 0, 1, 2
+
+
+def sample_interval(npairs: int, every: int = 100) -> int:
+    """Every how many pairs `smalt sample -u every` maps one (insSetSamplingInterval, insert.c:192-205)."""
+    return lib().smaltgpu_sample_interval(npairs, every)
+
+
+class InsertHistogram:
+    """Histogram of the insert sizes of a read-pair library (smaltgpu_inshist): what `smalt sample` writes and
+    `smalt map -g` reads.  Host code; needs no device."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    @classmethod
+    def from_sample(cls, sizes: Sequence[int]) -> "InsertHistogram":
+        arr = (C.c_int32 * max(1, len(sizes)))(*sizes)
+        h = C.c_void_p()
+        _check(lib().smaltgpu_inshist_from_sample(C.byref(h), arr, len(sizes)))
+        return cls(h)
+
+    @classmethod
+    def read(cls, path: str) -> "InsertHistogram":
+        h = C.c_void_p()
+        _check(lib().smaltgpu_inshist_read(C.byref(h), os.fsencode(path)))
+        return cls(h)
+
+    def text(self, what: int = HIST_SECTION, width: int = 80) -> bytes:
+        """HIST_SAMPLED / HIST_SMOOTHED: the bar print with lines of at most `width` bars; HIST_SECTION: the file section."""
+        t, n = C.c_void_p(), C.c_uint64()
+        _check(lib().smaltgpu_inshist_text(self.h, what, width, C.byref(t), C.byref(n)))
+        return C.string_at(t.value, n.value) if n.value else b""
+
+    def bounds(self):
+        """-> (smallest insert size, largest insert size, number of bins, number of sizes counted)"""
+        lo, hi, nb, tot = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+        _check(lib().smaltgpu_inshist_bounds(self.h, C.byref(lo), C.byref(hi), C.byref(nb), C.byref(tot)))
+        return lo.value, hi.value, nb.value, tot.value
+
+    def count(self, insert_size: int, smoothed: bool = True):
+        """-> (count of the bin of insert_size, cumulative count up to and including that bin)"""
+        c, cc = C.c_int32(), C.c_int32()
+        _check(lib().smaltgpu_inshist_count(self.h, insert_size, 1 if smoothed else 0, C.byref(c), C.byref(cc)))
+        return c.value, cc.value
+
+    def close(self):
+        if self.h:
+            lib().smaltgpu_inshist_free(self.h)
+            self.h = None
 
 
 class Index:

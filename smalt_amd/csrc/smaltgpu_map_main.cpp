@@ -9,6 +9,9 @@
 // Three stages run side by side: one thread parses the next block of the (memory-mapped) input, two threads own a
 // mapper each and take blocks in turn (host copies of one block overlap the kernels of the other), the main thread
 // formats and writes the blocks in input order.
+//
+// `smaltgpu-map sample` is `smalt sample` (mapReads with MENU_SAMPLE, smalt.c:1395-1410): the pairs are counted in a pass of its
+// own, every n-th pair goes through the same stages, and the histogram of the insert sizes follows the SAM lines.
 #include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -59,12 +62,39 @@ void usage() {
           "             two mappers (SMALTGPU_MAP_WORKERS: 1-4), blocks go to whichever is free\n"
           "  -i <int>   maximum insert size of read pairs (default 500); -j <int> minimum insert size (default 0)\n"
           "  -l <lib>   pair library: pe (default) | mp | pp\n"
+          "  -I <file>  histogram of insert sizes written by `sample` (the reference's `smalt map -g <file>`; -g names the devices here):\n"
+          "             it widens the insert range and weighs the pairings of a pair; its two prints go to standard output\n"
           "with two read files the reads are mapped as pairs (read i of the first with read i of the second file);\n"
-          "-w, -a and insert-size histograms (-g) go through the bound reference program (INTEGRATION.md)\n");
+          "-w and -a go through the bound reference program (INTEGRATION.md)\n"
+          "\n"
+          "usage: smaltgpu-map sample [-m <int>] [-n <int>] [-o <file>] [-q <int>] [-u <int>] [-B <int>] [-g <list>] <index prefix> <reads> <mates>\n"
+          "  `smalt sample`: maps every <u>-th pair (default 100; every (pairs / 4098)-th when that is fewer) and writes the SAM lines\n"
+          "  of these pairs, the sampled and the smoothed histogram of their insert sizes and the section that -I reads\n");
   exit(2);
 }
 
+// the sampled reads of one mate file, copied out of the parsed stretches of the input (sample)
+struct Kept {
+  std::vector<uint8_t> bases, quals;
+  std::vector<uint64_t> read_off, name_off;
+  std::vector<char> names;
+  bool has_qual = true;
+  void clear() { bases.clear(); quals.clear(); names.clear(); read_off.assign(1, 0); name_off.assign(1, 0); has_qual = true; }
+  void add(const smaltgpu_reads_view &v, uint32_t i) {
+    bases.insert(bases.end(), v.bases + v.read_off[i], v.bases + v.read_off[i + 1]);
+    if (v.has_qual && v.quals) quals.insert(quals.end(), v.quals + v.read_off[i], v.quals + v.read_off[i + 1]); else has_qual = false;
+    names.insert(names.end(), v.names + v.name_off[i], v.names + v.name_off[i + 1]);
+    read_off.push_back(bases.size()); name_off.push_back(names.size());
+  }
+  void view(smaltgpu_reads_view *v) const {
+    v->nreads = (uint32_t)(read_off.size() - 1); v->has_qual = has_qual && v->nreads ? 1 : 0;
+    v->bases = bases.data(); v->quals = v->has_qual ? quals.data() : nullptr; v->read_off = read_off.data();
+    v->names = names.data(); v->name_off = name_off.data(); v->consumed = 0;
+  }
+};
+
 struct Block {                                  // one block of reads (or pairs) on its way through the stages
+  Kept kept[2];
   smaltgpu_reads *rs = nullptr, *rs2 = nullptr;
   smaltgpu_reads_view v, v2;                    // v2: the mates
   smaltgpu_pairs *pairs = nullptr;
@@ -127,24 +157,31 @@ struct Source {
     return buf.data() + boff;
   }
   void consume(uint64_t n) { if (gz) boff += n; else pos += n; }
+  void close() {
+    if (gz) inflateEnd(&zs);
+    if (maplen) munmap((void *)map, maplen);
+    *this = Source();
+  }
   bool done() const { return gz ? (gz_end && boff >= buf.size()) : pos >= maplen; }
 };
 
 }  // namespace
 
 int main(int argc, char **argv) {
-  const char *fmt = "cigar", *oufil = nullptr, *scorespec = nullptr;
-  int m = -1, d = 0, seed = 0, q = 0, nthreads = 0, ins_max = 500, ins_min = 0, lib = SMALTGPU_LIB_PE;
+  const bool sampling = argc > 1 && !strcmp(argv[1], "sample");
+  const char *fmt = sampling ? "sam:nohead" : "cigar", *oufil = nullptr, *scorespec = nullptr, *histfil = nullptr;   // sample prints SAM lines without a header
+  int m = -1, d = 0, seed = 0, q = 0, nthreads = 0, ins_max = 500, ins_min = 0, lib = SMALTGPU_LIB_PE, every = 100;    // -u: MENU_DEFAULTS_READSKIP (menu.c:618)
   std::vector<int> devices;
   bool d_given = false, randrepeat = true, exhaustive = false, split = false;
   double minid = 0.0, mincover = 0.0;
   long batch = 262144;
-  int a = 1;
+  int a = sampling ? 2 : 1;
   for (; a < argc && argv[a][0] == '-' && argv[a][1]; a++) {
     const char o = argv[a][1];
     if (o == 'x' && !argv[a][2]) { exhaustive = true; continue; }
     if (o == 'p' && !argv[a][2]) { split = true; continue; }
-    if (argv[a][2] || !strchr("fomdrycqnBgijlS", o)) {
+    if (sampling && !strchr("mnoquBg", o)) usage();
+    if (argv[a][2] || !strchr("fomdrycqnBgijlSIu", o) || (o == 'u' && !sampling)) {
       if (strchr("wTFa", o) && !argv[a][2]) die("option not supported by this program (use the bound `smalt map`, INTEGRATION.md)", argv[a]);
       usage();
     }
@@ -164,14 +201,32 @@ int main(int argc, char **argv) {
       case 'j': ins_min = atoi(val); break;
       case 'l': lib = !strcmp(val, "pe") ? SMALTGPU_LIB_PE : !strcmp(val, "mp") ? SMALTGPU_LIB_MP : !strcmp(val, "pp") ? SMALTGPU_LIB_PP : 0; if (!lib) die("-l: pe, mp or pp"); break;
       case 'S': scorespec = val; break;
+      case 'I': histfil = val; break;
+      case 'u': every = atoi(val); break;
       case 'B': batch = atol(val); if (batch < 1 || batch > (1L << 20)) die("-B out of range (1 .. 1048576)"); break;
       case 'g': for (const char *c = val; *c;) { devices.push_back(atoi(c)); while (*c && *c != ',') c++; if (*c) c++; } break;
     }
   }
+  if (sampling && argc - a != 3) die("sample: expected an index prefix and two read files (insert sizes need read pairs)");
   if (argc - a != 2 && argc - a != 3) usage();
   const char *prefix = argv[a], *readfil = argv[a + 1], *matefil = argc - a == 3 ? argv[a + 2] : nullptr;
   const bool paired = matefil != nullptr;
   if (paired && ins_min > ins_max) die("-j above -i");
+  smaltgpu_inshist *hist = nullptr;
+  if (histfil) {                                                                         // smalt.c:556-571
+    if (smaltgpu_inshist_read(&hist, histfil)) die("-I", smaltgpu_last_error());
+    for (int what : {SMALTGPU_HIST_SAMPLED, SMALTGPU_HIST_SMOOTHED}) {
+      const char *t; uint64_t tl;
+      if (smaltgpu_inshist_text(hist, what, 80, &t, &tl)) die("-I", smaltgpu_last_error());
+      fwrite(t, 1, tl, stdout);
+    }
+    fflush(stdout);
+    int32_t lo, hi;
+    smaltgpu_inshist_bounds(hist, &lo, &hi, nullptr, nullptr);
+    if (lo < ins_min) ins_min = lo;
+    if (hi > ins_max) ins_max = hi;
+  }
+  if (sampling) { exhaustive = true; lib = SMALTGPU_LIB_ANY; randrepeat = false; }         // checkSampleDefaults (menu.c:1228-1252): -x, no -l, no draws
   if (nthreads < 1) { nthreads = (int)std::thread::hardware_concurrency(); if (nthreads > 16) nthreads = 16; if (nthreads < 1) nthreads = 1; }
 
   smaltgpu_report_opts ro;
@@ -203,6 +258,32 @@ int main(int argc, char **argv) {
   if (ro.outflags & SMALTGPU_OUT_RANDSEL) srand48(seed <= 0 ? (long)time(nullptr) : (long)seed);     // RANSEED (randef.h:19)
 
   Source src, src2;                                                                      // input: plain or gzip text
+  uint32_t interval = 1;
+  if (sampling) {
+    // the pairs are counted in a pass of their own (prepSample, smalt.c:1253-1286), gzip input is inflated twice
+    uint64_t count[2] = {0, 0};
+    for (int w = 0; w < 2; w++) {
+      Source sc;
+      sc.open(w ? matefil : readfil);
+      smaltgpu_reads *rs = smaltgpu_reads_create();
+      uint64_t win = 1u << 24;
+      for (;;) {
+        uint64_t got = 0; bool last = false;
+        const char *text = sc.window(win, &got, &last);
+        if (!got) break;
+        smaltgpu_reads_view v;
+        if (smaltgpu_reads_parse(rs, text, got, last ? 1 : 0, 0, nthreads, &v)) die("cannot parse the reads", smaltgpu_last_error());
+        if (!v.nreads && !last) { win *= 4; continue; }
+        count[w] += v.nreads;
+        sc.consume(v.consumed);
+        if (last) break;
+      }
+      smaltgpu_reads_free(rs);
+      sc.close();
+    }
+    if (count[0] != count[1]) die("the two read files hold different numbers of reads");
+    interval = (uint32_t)smaltgpu_sample_interval(count[0], every);
+  }
   src.open(readfil);
   if (paired) src2.open(matefil);
   FILE *ou = oufil ? fopen(oufil, "w") : stdout;
@@ -264,6 +345,7 @@ int main(int argc, char **argv) {
   if (!(par.rmapflg & SMALTGPU_FLG_SEQBYSEQ) && !packed) die("index", smaltgpu_last_error());
 
   smaltgpu_report *rep = smaltgpu_report_create();
+  if (hist && smaltgpu_report_set_inshist(rep, hist)) die("-I", smaltgpu_last_error());
   {
     const char *htxt; uint64_t hlen;
     if (smaltgpu_report_header(rep, seqnames, sop, nseq, &ro, "smaltgpu-map", VERSION, argc, (const char *const *)argv, &htxt, &hlen)) die("header", smaltgpu_last_error());
@@ -294,6 +376,7 @@ int main(int argc, char **argv) {
   uint32_t longest_so_far = 0;
   std::thread parser([&] {
     double bytes_per_read = 0.0;
+    uint64_t pairs_seen = 0;
     for (uint64_t k = 0;; k++) {
       Block &b = blk[k % NBLK];
       { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return failed || k < n_written + NBLK; }); if (failed) return; }
@@ -314,8 +397,27 @@ int main(int argc, char **argv) {
           w *= 4;                                          // not enough complete records in the window
         }
       };
-      if (!parse_from(src, b.rs, &b.v, (uint32_t)batch, false)) return;
-      if (paired && b.v.nreads) {
+      if (sampling) {
+        // stretches of the input are parsed until a block of sampled pairs is full: pair i is kept when i % interval == 0 (smalt.c:809-818)
+        b.kept[0].clear(); b.kept[1].clear();
+        for (;;) {
+          if (!parse_from(src, b.rs, &b.v, (uint32_t)batch, false)) return;
+          if (!parse_from(src2, b.rs2, &b.v2, b.v.nreads ? b.v.nreads : 1, true)) return;
+          if (b.v2.nreads != b.v.nreads) { std::lock_guard<std::mutex> lk(mu); b.err = "the two read files hold different numbers of reads"; failed = true; cv.notify_all(); return; }
+          if (!b.v.nreads) break;
+          for (uint32_t i = 0; i < b.v.nreads; i++)
+            if ((pairs_seen + i) % interval == 0) { b.kept[0].add(b.v, i); b.kept[1].add(b.v2, i); }
+          pairs_seen += b.v.nreads;
+          bytes_per_read = (double)b.v.consumed / (double)b.v.nreads;
+          win = (uint64_t)(bytes_per_read * (double)batch * 1.05) + 65536;
+          src.consume(b.v.consumed);
+          src2.consume(b.v2.consumed);
+          if (b.kept[0].read_off.size() - 1 + (uint64_t)batch / interval >= (uint64_t)batch) break;      // another stretch would not fit
+        }
+        b.kept[0].view(&b.v); b.kept[1].view(&b.v2);
+      } else if (!parse_from(src, b.rs, &b.v, (uint32_t)batch, false)) return;
+      if (sampling) {                                      // both files are parsed above
+      } else if (paired && b.v.nreads) {
         if (!parse_from(src2, b.rs2, &b.v2, b.v.nreads, true)) return;
         if (b.v2.nreads != b.v.nreads) { std::lock_guard<std::mutex> lk(mu); b.err = "the two read files hold different numbers of reads"; failed = true; cv.notify_all(); return; }
       } else if (paired) {
@@ -325,9 +427,11 @@ int main(int argc, char **argv) {
       }
       if (!b.v.nreads) { std::lock_guard<std::mutex> lk(mu); n_blocks_total = k; input_done = true; cv.notify_all(); return; }
       t_parse += now() - tp0;
-      bytes_per_read = (double)b.v.consumed / (double)b.v.nreads;
-      src.consume(b.v.consumed);
-      if (paired) src2.consume(b.v2.consumed);
+      if (!sampling) {
+        bytes_per_read = (double)b.v.consumed / (double)b.v.nreads;
+        src.consume(b.v.consumed);
+        if (paired) src2.consume(b.v2.consumed);
+      }
       b.maxlen = 1;
       for (uint32_t i = 0; i < b.v.nreads; i++) { const uint32_t l = (uint32_t)(b.v.read_off[i + 1] - b.v.read_off[i]); if (l > b.maxlen) b.maxlen = l; }
       if (paired) for (uint32_t i = 0; i < b.v2.nreads; i++) { const uint32_t l = (uint32_t)(b.v2.read_off[i + 1] - b.v2.read_off[i]); if (l > b.maxlen) b.maxlen = l; }
@@ -400,6 +504,7 @@ int main(int argc, char **argv) {
   for (int w = 0; w < NWORK; w++) workers.emplace_back(work, w);
 
   std::string failure;
+  std::vector<int32_t> sample;                              // insert sizes of the sampled pairs that have one (insAddSample, smalt.c:850-854)
   uint64_t nreads_total = 0;
   double t_emit = 0, t_write = 0, t_wait = 0;
   for (uint64_t k = 0;; k++) {
@@ -418,6 +523,11 @@ int main(int argc, char **argv) {
     t1 = now(); t_emit += t1 - t0; t0 = t1;
     if (failure.empty() && tl && fwrite(txt, 1, tl, ou) != tl) failure = "write error";
     t_write += now() - t0;
+    if (sampling && failure.empty()) {
+      const int32_t *isz; const uint8_t *known; uint32_t np;
+      if (smaltgpu_report_pair_inserts(rep, &isz, &known, &np)) failure = why("no insert sizes");
+      else for (uint32_t i = 0; i < np; i++) if (known[i]) sample.push_back(isz[i]);
+    }
     nreads_total += b.v.nreads;
     { std::lock_guard<std::mutex> lk(mu); b.state = 0; if (!paired) wk[b.worker].busy = false; n_written = k + 1; if (!failure.empty()) failed = true; cv.notify_all(); }
     if (!failure.empty()) break;
@@ -428,7 +538,24 @@ int main(int argc, char **argv) {
   if (failed && failure.empty()) for (Block &x : blk) if (!x.err.empty()) failure = x.err;
   for (Worker &W : wk) { if (W.mp) smaltgpu_mapper_free(W.mp); if (W.post) smaltgpu_post_free(W.post); }
   for (Block &b : blk) { smaltgpu_reads_free(b.rs); if (b.rs2) smaltgpu_reads_free(b.rs2); if (b.pairs) smaltgpu_pairs_free(b.pairs); }
+  if (sampling && !failed && failure.empty()) {             // outputHisto (smalt.c:1288-1310)
+    smaltgpu_inshist *sh = nullptr;
+    std::string tail;
+    const bool have = smaltgpu_inshist_from_sample(&sh, sample.data(), sample.size()) == 0;
+    const char *title[3] = {"# Sampled histogram\n", "# Smoothed histogram\n", ""};
+    const int what[3] = {SMALTGPU_HIST_SAMPLED, SMALTGPU_HIST_SMOOTHED, SMALTGPU_HIST_SECTION};
+    for (int j = 0; j < 3; j++) {
+      tail += title[j];
+      const char *t; uint64_t tl;
+      if (!have) { if (j < 2) tail += "# Histogram of insert sizes is empty.\n"; }
+      else if (smaltgpu_inshist_text(sh, what[j], 80, &t, &tl)) failure = why("cannot print the histogram");
+      else tail.append(t, tl);
+    }
+    if (failure.empty() && fwrite(tail.data(), 1, tail.size(), ou) != tail.size()) failure = "write error";
+    smaltgpu_inshist_free(sh);
+  }
   smaltgpu_report_free(rep);
+  smaltgpu_inshist_free(hist);
   for (smaltgpu_index *x : ixs) smaltgpu_index_free(x);
   if (ou != stdout) { if (fclose(ou)) failure = "write error"; } else fflush(ou);
   if (failed || !failure.empty()) die("failed", failure.c_str());

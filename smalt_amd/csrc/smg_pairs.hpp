@@ -16,13 +16,15 @@
 //   CHOICE      a weight per pairing from the two mapping probabilities and a prior for the layout; the heaviest pairing
 //               is reported with mapping qualities from the weight its alignments hold among all pairings; when it holds
 //               no more than 60 % the pair is ambiguous and -r decides what is printed (scorePairsSimple resultpairs.c:830,
-//               resultSetAddPairToReport :1222).
+//               resultSetAddPairToReport :1222).  With a histogram of insert sizes (smalt map -g) the prior of an oriented,
+//               in-range pairing follows the histogram when the pair has several pairings.
 // Walks over a table go segment by segment in score order (resultSetDo, results.c:2184): a visitor may end the current
 // segment or the whole walk.  Several rules only hold in that order -- in particular the PROBE's interval cursor, which
 // only moves forward and starts over when it has run off the end -- so the order is part of the rule.
 #ifndef SMG_PAIRS_HPP
 #define SMG_PAIRS_HPP
 #include <limits.h>
+#include "smg_inshist.hpp"
 #include "smg_post.hpp"
 
 namespace smgpairs {
@@ -317,8 +319,8 @@ inline int quality_of_probability(double p) {                  // results.c:292-
 
 struct Entry { int a, b; int quality_a, quality_b; uint8_t know; };     // one reported pairing: rows (-1: none) and what is printed with them
 
-// -> the pairings to print, the chosen one first.  `join.pairs` is re-ordered by weight.
-inline void choose(std::vector<Entry> &out, Join &join, Table &A, Table &B, uint8_t state, uint32_t policy, Draws &dr) {
+// -> the pairings to print, the chosen one first.  `join.pairs` is re-ordered by weight.  hist: the library's insert sizes, or nullptr
+inline void choose(std::vector<Entry> &out, Join &join, Table &A, Table &B, uint8_t state, uint32_t policy, Draws &dr, const smginshist::Histogram *hist = nullptr) {
   static const double TINY = 1E-7, P_DISORIENTED = 1e-4, P_OUT_OF_RANGE = 3e-3;            // resultpairs.c:134-136
   out.clear();
   std::vector<MatePair> &pr = join.pairs;
@@ -340,8 +342,19 @@ inline void choose(std::vector<Entry> &out, Join &join, Table &A, Table &B, uint
       if (state & PAIR_READ_RESTRICTED) { if (pa > pb) pa = pb; }
       else if (state & PAIR_MATE_RESTRICTED) { if (pb > pa) pb = pa; }
       double prior;
-      if (m.know & PM_ORIENTED) { prior = p_oriented; prior *= (m.know & PM_IN_RANGE) ? p_inside : P_OUT_OF_RANGE; }
-      else prior = P_DISORIENTED;
+      if (!(m.know & PM_ORIENTED)) prior = P_DISORIENTED;
+      else if (!(m.know & PM_IN_RANGE)) prior = p_oriented * P_OUT_OF_RANGE;
+      else if (!hist || pr.size() < 2) prior = p_oriented * p_inside;
+      else {
+        // the share of the library at or below this template length (smoothed counts over the counted sizes; an empty histogram
+        // counts as 1 of 1).  From one half on the share REPLACES the orientation prior by half of what lies above it
+        // (resultpairs.c:788-803)
+        int32_t below = hist->cumulative_of(m.tlen < 0 ? -m.tlen : m.tlen, true), all = (int32_t)hist->total;
+        if (all < 1) all = below = 1;
+        const double share = ((double)below) / all;
+        prior = share >= 0.5 ? 0.5 - share / 2 : p_oriented;
+        prior *= share * p_inside + P_OUT_OF_RANGE;
+      }
       m.weight = pa * pb * prior;
       total += m.weight;
       // a mate with one alignment only could also be placed wrongly altogether

@@ -637,7 +637,12 @@ bool print_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a, con
 
 }  // namespace
 
-struct smaltgpu_report { std::string text; std::vector<std::string> part; std::vector<int> draw; std::vector<uint32_t> seqlen; };
+struct smaltgpu_report {
+  std::string text; std::vector<std::string> part; std::vector<int> draw; std::vector<uint32_t> seqlen;
+  const smaltgpu_inshist *hist = nullptr;                          // smaltgpu_report_set_inshist
+  std::vector<int32_t> insert_size; std::vector<uint8_t> insert_known;      // per pair of the last smaltgpu_report_emit_pairs
+  uint32_t npairs_emitted = 0;
+};
 
 namespace {
 int check_format(const smaltgpu_report *rp, const smaltgpu_report_opts *op, int64_t nseq) {
@@ -818,6 +823,7 @@ struct PairJob {
   ReadCtx cx[2];
   const smaltgpu_report_opts *op;
   const smaltgpu_pair_opts *po;
+  const smginshist::Histogram *hist;
 };
 
 // everything for pair p up to the choice; -> number of random draws the choice needs (counting mode: dr.values == nullptr)
@@ -832,7 +838,22 @@ bool pair_entries(const PairJob &jb, uint32_t p, Table &A, Table &B, smgpairs::J
     A.apply_output_filter(jb.op->min_swscor, jb.op->min_swscor_below_max, jb.op->min_identity, (uint32_t)(jb.cx[0].rv->read_off[p + 1] - jb.cx[0].rv->read_off[p]));
     B.apply_output_filter(jb.op->min_swscor, jb.op->min_swscor_below_max, jb.op->min_identity, (uint32_t)(jb.cx[1].rv->read_off[p + 1] - jb.cx[1].rv->read_off[p]));
   }
-  smgpairs::choose(entries, join, A, B, pl.state, jb.op->outflags, dr);
+  smgpairs::choose(entries, join, A, B, pl.state, jb.op->outflags, dr, jb.hist);
+  return true;
+}
+
+// the insert size a pair adds to the sample of `smalt sample`: the template length of the best alignments of both mates when both
+// have a mapping quality of at least 20, taken behind the report of the pair (resultSetInferInsertSize, results.c:2460-2483).  The
+// test for a common sequence compares the read's sequence with itself there, so any two placed alignments count; the sign turns
+// for a reversed read ahead of a forward mate on ANOTHER sequence only (the layout flags must equal "read reversed" alone)
+bool sampled_insert(const Table &A, const Table &B, int32_t *size) {
+  *size = 0;
+  if (A.by_score.empty() || B.by_score.empty()) return false;
+  const uint32_t a = (uint32_t)A.by_score[0], b = (uint32_t)B.by_score[0];
+  if (A.quality[a] < smgpairs::QUALITY_CONFIDENT_FIRST || B.quality[b] < smgpairs::QUALITY_CONFIDENT_FIRST || A.seq[a] < 0) return false;
+  const smgpairs::Layout y = smgpairs::layout_of(A, a, B, b);
+  *size = y.tlen;
+  if (y.read_reversed && !y.mate_reversed && !y.mate_leftmost && !y.same_sequence && B.seq[b] >= 0) *size = -*size;
   return true;
 }
 
@@ -863,7 +884,11 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
   const uint32_t n = pairs->blk.npairs;
   if (reads->nreads != n || mates->nreads != n) return smaltgpu_set_error(SMALTGPU_EARG, "smaltgpu_report_emit_pairs: reads, mates and mapped pairs differ in number");
   if (int e = check_format(rp, op, nseq)) return e;
-  PairJob jb{pairs, {ReadCtx{nullptr, reads, op, seqnames, nseq, rp->seqlen.data()}, ReadCtx{nullptr, mates, op, seqnames, nseq, rp->seqlen.data()}}, op, po};
+  PairJob jb{pairs, {ReadCtx{nullptr, reads, op, seqnames, nseq, rp->seqlen.data()}, ReadCtx{nullptr, mates, op, seqnames, nseq, rp->seqlen.data()}}, op, po,
+             rp->hist ? &rp->hist->h : nullptr};
+  rp->insert_size.assign(n ? n : 1, 0);
+  rp->insert_known.assign(n ? n : 1, 0);
+  rp->npairs_emitted = n;
   if (nthreads < 1) nthreads = 1;
   if ((uint32_t)nthreads > n / 256 + 1) nthreads = (int)(n / 256 + 1);
   const bool drawing = (op->outflags & SMALTGPU_OUT_RANDSEL) != 0;
@@ -888,6 +913,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
       const uint64_t at = o.size();
       if (!pair_lines(o, jb, p, A, B, entries, sh)) { if (bad[(size_t)t] < 0) bad[(size_t)t] = p; continue; }
       where[p] = Slice{(uint32_t)t, at, o.size() - at};
+      rp->insert_known[p] = sampled_insert(A, B, &rp->insert_size[p]) ? 1 : 0;
     }
   };
   {
@@ -924,5 +950,18 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
   rp->text.reserve(tot);
   for (uint32_t p = 0; p < n; p++) rp->text.append(rp->part[where[p].part], where[p].at, where[p].len);
   *text = rp->text.data(); *len = rp->text.size();
+  return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_report_set_inshist(smaltgpu_report *rp, const smaltgpu_inshist *h) {
+  if (!rp) return smaltgpu_set_error(SMALTGPU_EARG, "smaltgpu_report_set_inshist: null argument");
+  rp->hist = h;
+  return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_report_pair_inserts(const smaltgpu_report *rp, const int32_t **insert_size, const uint8_t **known, uint32_t *npairs) {
+  if (!rp || !insert_size || !known || !npairs) return smaltgpu_set_error(SMALTGPU_EARG, "smaltgpu_report_pair_inserts: null argument");
+  *insert_size = rp->insert_size.data(); *known = rp->insert_known.data();
+  *npairs = (uint32_t)rp->npairs_emitted;
   return SMALTGPU_OK;
 }
