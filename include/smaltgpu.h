@@ -25,16 +25,27 @@ enum {
   SMALTGPU_ECAP = -5,       /* a work pool overflowed: smaltgpu_map_batch recovers by itself (reads re-mapped in smaller batches);
                              * from smaltgpu_fetch_* / in stat[].errcode it marks the reads to map again */
   SMALTGPU_EINTERNAL = -6,  /* device-side assertion (ERRCODE_ASSERT analogue) */
-  SMALTGPU_ESCORE = -8      /* in stat[].errcode: the traceback of one of the read's alignments does not add up to the score of its pass.
+  SMALTGPU_ESCORE = -8,     /* in stat[].errcode: the traceback of one of the read's alignments does not add up to the score of its pass.
                              * The reference stops at such a read with ERRCODE_SWATSCOR (alignment.c:767, "Inconsistency when calculating
                              * Smith-Waterman scores"): it happens with alignment scores (-S) whose gap extension is much cheaper than
                              * the opening, because the banded passes do not re-open a gap from a gap cell (alignment.c:1126-1193) */
+  SMALTGPU_ECPLX = -9       /* in stat[].errcode, with SMALTGPU_FLG_CMPLXW only: the complexity-weighted score of one of the read's alignments
+                             * came out above the unweighted one.  The reference stops at such a read with ERRCODE_CPLXSCOR (alignment.c:290-299,
+                             * "complexity weighted score exceeds unweighted score"): its constant for ln(1/4) is cut off at six digits, so an
+                             * alignment over an exactly balanced composition (say 1000 each of A, C, G, T) gains a fraction of a point.
+                             * A per-read code: every other read of the batch is complete */
 };
 /* return values of the mapping calls that mean "the batch is complete, some reads carry a code of their own in stat[].errcode" */
-#define SMALTGPU_IS_READ_ERROR(rv) ((rv) == SMALTGPU_ECAP || (rv) == SMALTGPU_EINTERNAL || (rv) == SMALTGPU_ESCORE)
+#define SMALTGPU_IS_READ_ERROR(rv) ((rv) == SMALTGPU_ECAP || (rv) == SMALTGPU_EINTERNAL || (rv) == SMALTGPU_ESCORE || (rv) == SMALTGPU_ECPLX)
 
 /* RMAP_FLAGS subset honoured on this path (same values as rmap.h:53-65). */
 enum {
+  SMALTGPU_FLG_CMPLXW = 0x01,    /* complexity-weighted alignment scores (smalt map -w, RMAPFLG_CMPLXW): honoured by every mapping call, the rounds of
+                                  * smaltgpu_map_pairs and both calls of smaltgpu_map_split included.  The score of every alignment of the traceback
+                                  * pass is scaled by the composition of the reference letters it pairs (scaleALICPLX, alignment.c:268-305) before it
+                                  * is compared with the threshold; swatscor, the score maxima and everything behind them see the weighted score.
+                                  * The first-pass scores (max1scor) stay unweighted, as in the reference.  Bit-identical to the reference:
+                                  * logarithms from a host-made table, lambda from the host, no fused multiply-adds */
   SMALTGPU_FLG_BEST = 0x02,
   SMALTGPU_FLG_SPLIT = 0x08,     /* split reads: honoured by smaltgpu_map_pairs (second calls of both mates ahead of the pairing, rmap.c:2073-2097);
                                   * the mapping calls themselves ignore it -- for single reads the two calls are smaltgpu_map_split */

@@ -15,7 +15,9 @@ from typing import List, Optional, Sequence
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBPATH = os.path.join(HERE, "libsmaltgpu.so")
 
-FLG_BEST, FLG_SEQBYSEQ, FLG_NOSHRTINFO, FLG_SENSITIVE = 0x02, 0x10, 0x20, 0x80
+FLG_CMPLXW, FLG_BEST, FLG_SEQBYSEQ, FLG_NOSHRTINFO, FLG_SENSITIVE = 0x01, 0x02, 0x10, 0x20, 0x80
+# codes of stat[].errcode (and of the mapping calls: the first one among the batch's reads)
+ECAP, EINTERNAL, ESCORE, ECPLX = -5, -6, -8, -9
 
 
 class SmaltGpuError(RuntimeError):
@@ -378,11 +380,11 @@ class Mapper:
     def map_batch(self, reads: Sequence[bytes], quals: Optional[Sequence[bytes]], params: Params, allow_read_errors: bool = False):
         """-> (list per read of result dicts in the reference's raw order, list of stat dicts).
         allow_read_errors: do not raise when single reads failed (device-side limit or the reference's own per-read
-        errors such as ERRCODE_SWATSCOR); their stat carries `err` and they have no results."""
+        errors ERRCODE_SWATSCOR and, with FLG_CMPLXW, ERRCODE_CPLXSCOR); their stat carries `err` and they have no results."""
         bases, q, off = self._pack(reads, quals)
         out = BatchOut()
         rv = lib().smaltgpu_map_batch(self.h, bases, q, off, len(reads), C.byref(params), C.byref(out))
-        if rv != 0 and not (allow_read_errors and rv in (-5, -6, -8) and out.nreads == len(reads)):
+        if rv != 0 and not (allow_read_errors and rv in (ECAP, EINTERNAL, ESCORE, ECPLX) and out.nreads == len(reads)):
             _check(rv)
         return self._unpack(out)
 

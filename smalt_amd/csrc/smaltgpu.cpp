@@ -316,6 +316,7 @@ struct smaltgpu_mapper {
                   CT_ALIGN_RETRY = 9 * CT_LINE, CT_CANDS_RETRY = 10 * CT_LINE, CT_HITS = 11 * CT_LINE, CT_HITS_CURSOR = 12 * CT_LINE, CT_STRIP_CURSOR = 13 * CT_LINE,
                   CT_WORK = 14 * CT_LINE /* 32 x 8 bytes */, CT_BYTES = 16 * CT_LINE };
   uint8_t *d_counters = nullptr;
+  double *d_logtab = nullptr; uint32_t logtab_n = 0;     // log(n), n <= max_len, for the complexity-weighted scores (SMALTGPU_FLG_CMPLXW; smg_cplx.hpp)
   uint8_t *seed_scr = nullptr; size_t seed_bytes = 0; uint32_t seed_slots = 0;
   uint8_t *cand_scr = nullptr; size_t cand_bytes = 0; uint32_t cand_slots = 0;
   CandGeom cg2; uint8_t *cand_scr2 = nullptr; size_t cand_bytes2 = 0; uint32_t cand_slots2 = 0;   // second pass of the candidate stage: full-size slots
@@ -442,6 +443,17 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
   if (b.dstrcap > 0xFFFFFFF0ull) b.dstrcap = 0xFFFFFFF0ull;    // smaltgpu_result.stroffs is 32 bits wide: a batch that needs more reports SMALTGPU_ECAP and is re-mapped in parts
   DA(b.dstrpool, b.dstrcap);
   DA(b.align_retry, max_batch_reads);
+  {
+    // complexity-weighted scores (SMALTGPU_FLG_CMPLXW): log(n) for every number of traceback steps a read of this mapper can have,
+    // from the host's libm -- the device multiplies and adds what the reference multiplies and adds (smg_cplx.hpp)
+    m->logtab_n = max_read_len + 1;
+    DA(m->d_logtab, m->logtab_n);
+    if (!rv) {
+      std::vector<double> h(m->logtab_n);
+      cplx_fill_logtab(h.data(), m->logtab_n);
+      if (hipMemcpy(m->d_logtab, h.data(), (size_t)m->logtab_n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "upload of the logarithm table failed");
+    }
+  }
   DA(b.cands_retry, max_batch_reads);
   DA(m->d_counters, smaltgpu_mapper::CT_BYTES);
   // S3 as a kernel of its own (k_hits) for mappers of short reads: sorted hit keys of every strand in one pool, 8 bytes per hit.
@@ -608,7 +620,7 @@ extern "C" void smaltgpu_mapper_free(smaltgpu_mapper *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   void *ps[] = {m->d_bases, m->d_quals, m->d_codes, m->d_codes_rc, m->d_off, m->d_ids, m->b.hi, m->b.seeds, m->b.qmask, m->b.ch, m->b.ctl,
-                m->b.stat, m->b.align_retry, m->b.cands_retry, m->b.hitpool, m->b_hitrun, m->b.rcpool, m->b.long_list, m->b.strip_list, m->strip_bnd, m->strip_win, m->b.respool, m->b.dstrpool, m->d_counters, m->seed_scr, m->cand_scr, m->cand_scr2, m->cand_scr_dbg,
+                m->b.stat, m->b.align_retry, m->b.cands_retry, m->d_logtab, m->b.hitpool, m->b_hitrun, m->b.rcpool, m->b.long_list, m->b.strip_list, m->strip_bnd, m->strip_win, m->b.respool, m->b.dstrpool, m->d_counters, m->seed_scr, m->cand_scr, m->cand_scr2, m->cand_scr_dbg,
                 m->sw_rows, m->align_scr, m->align_scr2};
   for (void *p : ps) if (p) (void)hipFree(p);
   m->h_stat.release(); m->h_res.release(); m->h_dstr.release();
@@ -709,8 +721,11 @@ static int run_pipeline(smaltgpu_mapper *m, const uint8_t *d_bases, const uint8_
   HIPCHK(hipEventRecord(m->ev[T_REPLAY], s));
   if (!rv) rv = launch_replay(s, b, d, p);
   HIPCHK(hipEventRecord(m->ev[T_ALIGN], s));
-  if (!rv) rv = launch_align(s, b, d, p, m->align_scr, m->align_bytes, m->align_slots, m->wincap, m->dircap, m->rescap_slot, m->dstrcap_slot, 1);
-  if (!rv) rv = launch_align(s, b, d, p, m->align_scr2, m->align_bytes2, m->align_slots2, m->wincap, m->dircap2, m->rescap_slot2, m->dstrcap_slot2, 2);
+  CplxPar cplx;
+  cplx.logtab = m->d_logtab; cplx.nlog = m->logtab_n; cplx.pad = 0;
+  cplx.lambda = (p.flags & FLG_CMPLXW) ? cplx_lambda(p.match, p.mismatch) : 0.0;        // createALICPLX (alignment.c:252)
+  if (!rv) rv = launch_align(s, b, d, p, m->align_scr, m->align_bytes, m->align_slots, m->wincap, m->dircap, m->rescap_slot, m->dstrcap_slot, 1, &cplx);
+  if (!rv) rv = launch_align(s, b, d, p, m->align_scr2, m->align_bytes2, m->align_slots2, m->wincap, m->dircap2, m->rescap_slot2, m->dstrcap_slot2, 2, &cplx);
   HIPCHK(hipEventRecord(m->ev[T_NUM], s));
   if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
   return SMALTGPU_OK;
@@ -812,7 +827,7 @@ extern "C" int smaltgpu_fetch_end(smaltgpu_mapper *m, smaltgpu_batch_out *out) {
     for (std::thread &x : th) x.join();
   }
   out->nreads = n; out->res_off = m->h_res_off.data(); out->res = m->o_res.data(); out->diffstr = m->h_dstr.data(); out->stat = m->o_stat.data();
-  if (first_err) return fail(first_err, "%u of %u reads hit a device-side limit (-5%s), an assertion (-6) or the reference's own score check (-8); first: read %u code %d (see stat[].errcode)", nerr, n,
+  if (first_err) return fail(first_err, "%u of %u reads hit a device-side limit (-5%s), an assertion (-6) or one of the reference's own score checks (-8, -9); first: read %u code %d (see stat[].errcode)", nerr, n,
                              m->pool_overflow ? ": a batch-wide work pool overflowed" : "", first_err_read, first_err);
   return SMALTGPU_OK;
 }

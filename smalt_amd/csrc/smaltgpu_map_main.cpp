@@ -54,6 +54,7 @@ void usage() {
           "  -c <num>   minimum k-mer cover (fraction of the read if <= 1, else bases)\n"
           "  -x         more sensitive search (all seeds, deeper candidate lists)\n"
           "  -p         split reads: a second alignment for the part of a read (or mate) its best alignment leaves uncovered\n"
+          "  -w         complexity-weighted alignment scores: an alignment over a low-complexity stretch of the reference scores less\n"
           "  -q <int>   base quality threshold for k-mer words\n"
           "  -S <spec>  alignment scores, e.g. match=1,subst=-2,gapopen=-4,gapext=-3 (the default; any subset)\n"
           "  -n <int>   host threads for parsing, post-processing and formatting (default: up to 16)\n"
@@ -65,7 +66,7 @@ void usage() {
           "  -I <file>  histogram of insert sizes written by `sample` (the reference's `smalt map -g <file>`; -g names the devices here):\n"
           "             it widens the insert range and weighs the pairings of a pair; its two prints go to standard output\n"
           "with two read files the reads are mapped as pairs (read i of the first with read i of the second file);\n"
-          "-w and -a go through the bound reference program (INTEGRATION.md)\n"
+          "-a goes through the bound reference program (INTEGRATION.md)\n"
           "\n"
           "usage: smaltgpu-map sample [-m <int>] [-n <int>] [-o <file>] [-q <int>] [-u <int>] [-B <int>] [-g <list>] <index prefix> <reads> <mates>\n"
           "  `smalt sample`: maps every <u>-th pair (default 100; every (pairs / 4098)-th when that is fewer) and writes the SAM lines\n"
@@ -172,7 +173,7 @@ int main(int argc, char **argv) {
   const char *fmt = sampling ? "sam:nohead" : "cigar", *oufil = nullptr, *scorespec = nullptr, *histfil = nullptr;   // sample prints SAM lines without a header
   int m = -1, d = 0, seed = 0, q = 0, nthreads = 0, ins_max = 500, ins_min = 0, lib = SMALTGPU_LIB_PE, every = 100;    // -u: MENU_DEFAULTS_READSKIP (menu.c:618)
   std::vector<int> devices;
-  bool d_given = false, randrepeat = true, exhaustive = false, split = false;
+  bool d_given = false, randrepeat = true, exhaustive = false, split = false, weighted = false;
   double minid = 0.0, mincover = 0.0;
   long batch = 262144;
   int a = sampling ? 2 : 1;
@@ -180,9 +181,10 @@ int main(int argc, char **argv) {
     const char o = argv[a][1];
     if (o == 'x' && !argv[a][2]) { exhaustive = true; continue; }
     if (o == 'p' && !argv[a][2]) { split = true; continue; }
+    if (o == 'w' && !argv[a][2] && !sampling) { weighted = true; continue; }       // (the reference's `sample` has no -w)
     if (sampling && !strchr("mnoquBg", o)) usage();
     if (argv[a][2] || !strchr("fomdrycqnBgijlSIu", o) || (o == 'u' && !sampling)) {
-      if (strchr("wTFa", o) && !argv[a][2]) die("option not supported by this program (use the bound `smalt map`, INTEGRATION.md)", argv[a]);
+      if (strchr("TFa", o) && !argv[a][2]) die("option not supported by this program (use the bound `smalt map`, INTEGRATION.md)", argv[a]);
       usage();
     }
     if (a + 1 >= argc) usage();
@@ -335,6 +337,7 @@ int main(int argc, char **argv) {
   par.min_swatscor_below_max = d;
   if (d) par.rmapflg &= ~(uint32_t)SMALTGPU_FLG_BEST;
   if (exhaustive) par.rmapflg |= SMALTGPU_FLG_NOSHRTINFO | SMALTGPU_FLG_SENSITIVE;      // smalt.c:531-533
+  if (weighted) par.rmapflg |= SMALTGPU_FLG_CMPLXW;                                      // smalt.c:513-514
   if (split) { par.rmapflg |= SMALTGPU_FLG_SPLIT | SMALTGPU_FLG_NOSHRTINFO | SMALTGPU_FLG_SENSITIVE; ro.outflags |= SMALTGPU_OUT_SPLIT; }      // smalt.c:507-511 (RMAPFLG_SPLIT: smaltgpu_map_split)
   par.min_basqval = (uint8_t)q;
   if (mincover < 1.01) { par.min_cover = 0; par.min_cover_frac = mincover; } else { par.min_cover = (uint32_t)mincover; par.min_cover_frac = 0.0; }   // smalt.c:1113-1126

@@ -13,7 +13,7 @@
 namespace smg {
 
 enum : int { IDX_PERFECT = 0, IDX_HASH32MIX = 1 };
-enum : uint32_t { FLG_BEST = 0x02, FLG_SEQBYSEQ = 0x10, FLG_NOSHRTINFO = 0x20, FLG_SENSITIVE = 0x80 };
+enum : uint32_t { FLG_CMPLXW = 0x01 /* complexity-weighted alignment scores (smalt map -w; smg_cplx.hpp) */, FLG_BEST = 0x02, FLG_SEQBYSEQ = 0x10, FLG_NOSHRTINFO = 0x20, FLG_SENSITIVE = 0x80 };
 // hit qualifiers per read offset (hashhit.h:57-65)
 enum : uint8_t { HQ_TERM = 0, HQ_NORMHIT = 1, HQ_MULTIHIT = 2, HQ_REPEAT = 3, HQ_NOHIT = 4, HQ_NONSTDNT = 5 };
 // HashHitInfo status bits (hashhit.c:84-92)
@@ -21,7 +21,8 @@ enum : uint32_t { HI_REVERSE = 1, HI_SORTED = 2, HI_RANK = 4 };
 enum : uint8_t { CANDFLG_REVERSE = 1, CANDFLG_MMALI = 4 };                 // segment.h:50-58
 enum : int { SMG_ERR_CAP = -5, SMG_ERR_ASSERT = -6,   // same values as SMALTGPU_ECAP / EINTERNAL
              SMG_ERR_RETRY = -7,     // internal: the read waits for the second K3 pass (large direction-matrix slots)
-             SMG_ERR_SCORE = -8 };   // = SMALTGPU_ESCORE: a traceback whose score is not the pass's maximum (the reference's ERRCODE_SWATSCOR)
+             SMG_ERR_SCORE = -8,     // = SMALTGPU_ESCORE: a traceback whose score is not the pass's maximum (the reference's ERRCODE_SWATSCOR)
+             SMG_ERR_CPLX = -9 };    // = SMALTGPU_ECPLX: a complexity-weighted score above the unweighted one (the reference's ERRCODE_CPLXSCOR)
 enum : uint32_t { RCF_REVERSE = 1, RCF_SCORED = 2, RCF_BANDED = 4, RCF_ERR = 8,
                   RCF_QN = 16 /* the read holds non-ACGT codes: K2a in 32-bit lanes */,
                   RCF_BSCORED = 32 /* swscor is the banded (K2b) score */ };

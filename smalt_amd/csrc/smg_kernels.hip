@@ -216,9 +216,11 @@ __global__ void __launch_bounds__(256) k_replay(Batch b, DevIndex ix, MapPar p) 
 }
 
 // K3: one wave per read; hot arrays in LDS, results and oversized direction matrices in the HBM slot
-template <bool WIDE>
+// CPLX: complexity-weighted scores (MapPar::flags & FLG_CMPLXW): a compile-time switch, so that the instances without it stay the code
+// they were; cp is the table of logarithms and lambda (CplxPar) for the weighted instances and an empty argument otherwise
+template <bool WIDE, bool CPLX = false>
 __global__ void __launch_bounds__(64) k_align(Batch b, DevIndex ix, MapPar p, uint8_t *gscratch, size_t gbytes, uint32_t wincap,
-                                              uint64_t dircap, uint32_t rescap, uint32_t dstrcap, uint32_t lds_bytes, int pass) {
+                                              uint64_t dircap, uint32_t rescap, uint32_t dstrcap, uint32_t lds_bytes, int pass, typename cplx_arg<CPLX>::type cp) {
   extern __shared__ __align__(16) uint8_t lds[];
   uint8_t *base = gscratch + gbytes * blockIdx.x;
   AlignScratch x = align_scratch_carve_lds(lds_bytes ? lds + LDS_GUARD : nullptr, lds_bytes, base, b.qmax, wincap, dircap, rescap, dstrcap);
@@ -232,14 +234,14 @@ __global__ void __launch_bounds__(64) k_align(Batch b, DevIndex ix, MapPar p, ui
   if (pass == 2) {                        // only the reads the first pass deferred (usually none: the launch ends at once)
     const uint32_t n = *b.align_retry_n;
     for (uint32_t i = next_item(cursor, &qslot); i < n; i = next_item(cursor, &qslot)) {
-      stage_align<WIDE>(b, ix, p, b.align_retry[i], x);
+      stage_align<WIDE, CPLX>(b, ix, p, b.align_retry[i], x, cp);
       __syncthreads();
     }
     align_tally_flush(b, x);
     return;
   }
   for (uint32_t r = next_item(cursor, &qslot); r < b.nreads; r = next_item(cursor, &qslot)) {
-    stage_align<WIDE>(b, ix, p, r, x);
+    stage_align<WIDE, CPLX>(b, ix, p, r, x, cp);
     __syncthreads();
   }
   align_tally_flush(b, x);
@@ -1343,7 +1345,7 @@ int launch_replay(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPa
 }
 
 int launch_align(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, size_t sbytes, uint32_t nslots,
-                 uint32_t wincap, uint64_t dircap, uint32_t rescap, uint32_t dstrcap, int pass) {
+                 uint32_t wincap, uint64_t dircap, uint32_t rescap, uint32_t dstrcap, int pass, const CplxPar *cplx) {
   if (!b.nreads) return 0;
   uint32_t grid = b.nreads < nslots ? b.nreads : nslots;
   size_t small = align_lds_small_bytes(b.qmax, wincap);
@@ -1353,8 +1355,13 @@ int launch_align(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar
   uint32_t lds_bytes = small + 4096 <= (size_t)kb * 1024 ? kb * 1024 - LDS_GUARD : 0;      // rows + window + direction bytes
   static const int antidiag = getenv("SMALTGPU_ALIGN_ANTIDIAG") ? 0x100 : 0;      // test hook: narrow bands in the anti-diagonal form (band_track_wave)
   pass |= antidiag;
-  if (b.qmax > 256) hipLaunchKernelGGL(k_align<true>, dim3(grid), dim3(64), lds_bytes ? lds_bytes + LDS_GUARD : 0, s, b, ix, p, scratch, sbytes, wincap, dircap, rescap, dstrcap, lds_bytes, pass);
-  else hipLaunchKernelGGL(k_align<false>, dim3(grid), dim3(64), lds_bytes ? lds_bytes + LDS_GUARD : 0, s, b, ix, p, scratch, sbytes, wincap, dircap, rescap, dstrcap, lds_bytes, pass);
+  const size_t dyn = lds_bytes ? lds_bytes + LDS_GUARD : 0;
+  if (p.flags & FLG_CMPLXW) {
+    if (!cplx || !cplx->logtab || !(cplx->lambda > 0.0)) return (int)hipErrorInvalidValue;      // the weighting needs its table and lambda: no launch without them
+    if (b.qmax > 256) hipLaunchKernelGGL((k_align<true, true>), dim3(grid), dim3(64), dyn, s, b, ix, p, scratch, sbytes, wincap, dircap, rescap, dstrcap, lds_bytes, pass, *cplx);
+    else hipLaunchKernelGGL((k_align<false, true>), dim3(grid), dim3(64), dyn, s, b, ix, p, scratch, sbytes, wincap, dircap, rescap, dstrcap, lds_bytes, pass, *cplx);
+  } else if (b.qmax > 256) hipLaunchKernelGGL((k_align<true, false>), dim3(grid), dim3(64), dyn, s, b, ix, p, scratch, sbytes, wincap, dircap, rescap, dstrcap, lds_bytes, pass, NoCplx());
+  else hipLaunchKernelGGL((k_align<false, false>), dim3(grid), dim3(64), dyn, s, b, ix, p, scratch, sbytes, wincap, dircap, rescap, dstrcap, lds_bytes, pass, NoCplx());
   SMG_LAUNCH_CHECK();
   return 0;
 }

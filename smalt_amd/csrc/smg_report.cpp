@@ -692,11 +692,12 @@ extern "C" int smaltgpu_report_emit(smaltgpu_report *rp, const smaltgpu_post_out
     if (raw && raw->stat[i].errcode) {               // the reference stops at a read that fails (rmap.c:1417 -> smalt.c: the message names the read)
       std::string m = "read '";
       first_word(m, reads->names + reads->name_off[i], false);
-      char t[160];
+      char t[224];
       snprintf(t, sizeof(t), "' (%u of its block) carries error code %d%s", i, raw->stat[i].errcode,
-               raw->stat[i].errcode == SMALTGPU_ESCORE ? ": inconsistency when calculating Smith-Waterman scores (the reference stops at this read with ERRCODE_SWATSCOR)" : "");
+               raw->stat[i].errcode == SMALTGPU_ESCORE ? ": inconsistency when calculating Smith-Waterman scores (the reference stops at this read with ERRCODE_SWATSCOR)" :
+               raw->stat[i].errcode == SMALTGPU_ECPLX ? ": complexity weighted score exceeds unweighted score (the reference stops at this read with ERRCODE_CPLXSCOR)" : "");
       m += t;
-      return smaltgpu_set_error(raw->stat[i].errcode == SMALTGPU_ESCORE ? SMALTGPU_ESCORE : SMALTGPU_EINTERNAL, m.c_str());
+      return smaltgpu_set_error(raw->stat[i].errcode == SMALTGPU_ESCORE || raw->stat[i].errcode == SMALTGPU_ECPLX ? raw->stat[i].errcode : SMALTGPU_EINTERNAL, m.c_str());
     }
   }
   // the random choices in read order, as one thread of the reference makes them (drand48 is the C library's shared sequence)

@@ -83,7 +83,7 @@ struct Runner {
       Table tb;
       for (uint32_t r = lo; r < hi; r++) {
         const smaltgpu_readstat &st = o.stat[r];
-        if (st.errcode) { complain(t, r, st.errcode == SMALTGPU_ESCORE ? "inconsistency when calculating Smith-Waterman scores: the reference stops at this read (ERRCODE_SWATSCOR)" : "the mapping call failed on the device", st.errcode, st.errsite); if (st.errcode == SMALTGPU_ESCORE) code_seen = SMALTGPU_ESCORE; continue; }
+        if (st.errcode) { complain(t, r, st.errcode == SMALTGPU_ESCORE ? "inconsistency when calculating Smith-Waterman scores: the reference stops at this read (ERRCODE_SWATSCOR)" : st.errcode == SMALTGPU_ECPLX ? "complexity weighted score exceeds unweighted score: the reference stops at this read (ERRCODE_CPLXSCOR)" : "the mapping call failed on the device", st.errcode, st.errsite); if (st.errcode == SMALTGPU_ESCORE || st.errcode == SMALTGPU_ECPLX) code_seen = st.errcode; continue; }
         tb.clear();
         tb.n_ali_done = st.n_ali_done; tb.n_ali_tot = st.n_ali_tot; tb.n_hits_used = st.n_hits_used; tb.n_hits_tot = st.n_hits_tot;
         tb.take_call(o.res + o.res_off[r], (uint32_t)(o.res_off[r + 1] - o.res_off[r]), o.diffstr, st.swatscor_max, st.swatscor_2ndmax);
@@ -124,7 +124,7 @@ struct Runner {
         for (uint32_t i = lo; i < hi; i++) {
           const uint32_t r = ids[i];
           const smaltgpu_readstat &st = o2.stat[i];
-          if (st.errcode) { complain(t, r, st.errcode == SMALTGPU_ESCORE ? "second call: inconsistency when calculating Smith-Waterman scores: the reference stops at this read (ERRCODE_SWATSCOR)" : "the second mapping call failed on the device", st.errcode, st.errsite); if (st.errcode == SMALTGPU_ESCORE) code_seen = SMALTGPU_ESCORE; continue; }
+          if (st.errcode) { complain(t, r, st.errcode == SMALTGPU_ESCORE ? "second call: inconsistency when calculating Smith-Waterman scores: the reference stops at this read (ERRCODE_SWATSCOR)" : st.errcode == SMALTGPU_ECPLX ? "second call: complexity weighted score exceeds unweighted score: the reference stops at this read (ERRCODE_CPLXSCOR)" : "the second mapping call failed on the device", st.errcode, st.errsite); if (st.errcode == SMALTGPU_ESCORE || st.errcode == SMALTGPU_ECPLX) code_seen = st.errcode; continue; }
           tb.unpack(rest.data(r), rest.size(r));
           tb.n_ali_done = st.n_ali_done; tb.n_ali_tot = st.n_ali_tot; tb.n_hits_used = st.n_hits_used; tb.n_hits_tot = st.n_hits_tot;     // rmap.c:1337
           tb.take_call(o2.res + o2.res_off[i], (uint32_t)(o2.res_off[i + 1] - o2.res_off[i]), o2.diffstr, st.swatscor_max, st.swatscor_2ndmax);

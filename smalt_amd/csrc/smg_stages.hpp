@@ -12,6 +12,7 @@
 #include "smg_exec.h"
 #include "smg_logic.hpp"
 #include "smg_wsort.hpp"
+#include "smg_cplx.hpp"
 
 namespace smg {
 
@@ -956,10 +957,15 @@ SMG_HD inline size_t dir_index(const Band &bp, int tW, int ip, int j) {
   return (size_t)(ip + (j - jmin)) * (size_t)tW + (size_t)((j - jmin) & (tW - 1));     // tW: a power of two
 }
 
+// CPLX: also count the reference letter under every diagonal step into cnt[CPLX_NCODES] (alignment.c:706-707; the counters
+// are compared and added one by one: an array indexed by the code would live in scratch memory on the device)
+template <bool CPLX = false>
 SMG_HD inline int traceback_scalar(uint8_t *ds, uint32_t dscap, int *qs, int *rs, const Band &bp, const uint8_t *dir,
                                    int max_i, int max_j, int max_scor, const uint8_t *q, const uint8_t *win,
-                                   const int8_t *M, int gi, int ge, int tW = 0, const StripGeom *sg = nullptr) {
+                                   const int8_t *M, int gi, int ge, int tW = 0, const StripGeom *sg = nullptr, int *cnt = nullptr) {
   uint32_t n = 0;
+  int cn0 = 0, cn1 = 0, cn2 = 0, cn3 = 0, cn4 = 0, cn5 = 0;
+#define SMG_CPLX_COUNT(code) { if (CPLX) { cn0 += (code) == 0; cn1 += (code) == 1; cn2 += (code) == 2; cn3 += (code) == 3; cn4 += (code) == 4; cn5 += (code) == 5; } }
   const int tb_match = M[0], tb_mismatch = M[1];   // (the matrix is read twice here, not once per step: it lives in scratch memory on the device)
   int c_sidx = -1, c_rlo = 0;                  // strip layout (tW < 0): directions come from strip_dir
   uint64_t c_base = 0;
@@ -980,6 +986,7 @@ SMG_HD inline int traceback_scalar(uint8_t *ds, uint32_t dscap, int *qs, int *rs
           else nmatch++;
         } else { SMG_PUT(nmatch, DIFF_S) nmatch = 0; }
         checksum += s;
+        SMG_CPLX_COUNT(rbc)
         gap_open = false;
         i--; j--;
         continue;
@@ -999,6 +1006,7 @@ SMG_HD inline int traceback_scalar(uint8_t *ds, uint32_t dscap, int *qs, int *rs
         else nmatch++;
       } else { SMG_PUT(nmatch, DIFF_S) nmatch = 0; }
       checksum += s;
+      SMG_CPLX_COUNT(rbc)
       gap_open = false;
       dp -= bp.band_width; i--; j--;
       continue;
@@ -1011,6 +1019,8 @@ SMG_HD inline int traceback_scalar(uint8_t *ds, uint32_t dscap, int *qs, int *rs
   SMG_PUT(nmatch, DIFF_S)
   SMG_PUT(0, DIFF_M)
 #undef SMG_PUT
+#undef SMG_CPLX_COUNT
+  if (CPLX) { cnt[0] = cn0; cnt[1] = cn1; cnt[2] = cn2; cnt[3] = cn3; cnt[4] = cn4; cnt[5] = cn5; }
   *rs = i + 1; *qs = j + 1;
   return (checksum != max_scor) ? -3 : (int)n;      // ERRCODE_SWATSCOR (alignment.c:767): the path's score is not the pass's maximum
 }
@@ -1259,14 +1269,18 @@ __device__ inline int band_track_rows_n(const Band &bp, PW q, PW win, int match,
 // ONE round: lane k looks at the cell k steps up the diagonal (its direction byte, reference and read base), a ballot finds where
 // the stretch ends and where it holds non-matches, and the string operations of the whole stretch are put together from those two
 // masks -- an alignment of a 150-base read with three mismatches takes about eight rounds instead of 150 dependent steps.
+// CPLX: the reference letters under the diagonal steps are counted as well (alignment.c:706-707): per round one ballot per letter
+// code, masked with the stretch, and its population count into a wave-uniform counter; cnt[CPLX_NCODES] is the same in all lanes.
+template <bool CPLX = false>
 __device__ inline int traceback_uniform(uint8_t *ds, uint32_t dscap, int *qs, int *rs, const Band &bp, const uint8_t *dir,
                                         int max_i, int max_j, int max_scor, const uint8_t *q, const uint8_t *win,
-                                        int tb_match, int tb_mismatch, int gi, int ge) {
+                                        int tb_match, int tb_mismatch, int gi, int ge, int *cnt = nullptr) {
 #define SMG_U(v) __builtin_amdgcn_readfirstlane((int)(v))
   const int bw = SMG_U(bp.band_width), s_left = SMG_U(bp.s_left), q_left = SMG_U(bp.q_left);
   int i = SMG_U(max_i), j = SMG_U(max_j);
   int off = (i - s_left) * (bw - 1) + (j - SMG_U(bp.l_edge));       // dir_index with tW == 0
   int n = 0, checksum = 0, nmatch = 0, rv = 0;
+  int cn[CPLX_NCODES] = {0, 0, 0, 0, 0, 0};
   bool gap_open = false;
   const bool writer = threadIdx.x == 0;
   const int cap = (int)dscap, lane = (int)threadIdx.x;
@@ -1294,6 +1308,10 @@ __device__ inline int traceback_uniform(uint8_t *ds, uint32_t dscap, int *qs, in
     unsigned long long stops = __ballot(sc <= 0) & inrun;            // steps that close a run of matches (substitution or a code without score)
     const unsigned long long minus = __ballot(sc < 0) & inrun;
     checksum += (run - (int)__builtin_popcountll(stops)) * tb_match + (int)__builtin_popcountll(minus) * tb_mismatch;
+    if (CPLX) {
+#pragma unroll
+      for (int c = 0; c < CPLX_NCODES; c++) cn[c] += (int)__builtin_popcountll(__ballot(rbc == c) & inrun);
+    }
     int pos = 0;
     for (;;) {
       const int nxt = stops ? (int)__builtin_ctzll(stops) : run;
@@ -1315,6 +1333,10 @@ __device__ inline int traceback_uniform(uint8_t *ds, uint32_t dscap, int *qs, in
   if (!rv) { SMG_PUTU(0, DIFF_M) }
 #undef SMG_PUTU
 #undef SMG_U
+  if (CPLX) {
+#pragma unroll
+    for (int c = 0; c < CPLX_NCODES; c++) cnt[c] = cn[c];
+  }
   if (rv) return rv;
   *rs = i + 1; *qs = j + 1;
   return (checksum != max_scor) ? -3 : n;
@@ -1392,8 +1414,11 @@ __device__ inline int band_track_wave_n(const Band &bp, PW q, PW win, int match,
 
 // WIDE: also instantiate the multi-column wave form for bands of more than 64 columns (long reads); it needs many
 // registers, so mappers for short reads use the lean instance and leave the rare wide band to the sequential form.
-template <bool WIDE = false>
-SMG_HD inline void stage_align(const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t r, AlignScratch &x) {
+// CPLX: complexity-weighted scores (FLG_CMPLXW, smalt map -w): the tracebacks count letters and the score of an alignment is
+// scaled (smg_cplx.hpp) before it is compared with the threshold and stored; the instances without it are the code they were.
+// cp: the table of logarithms and lambda (CplxPar) of the weighted instances; an empty argument otherwise.
+template <bool WIDE = false, bool CPLX = false>
+SMG_HD inline void stage_align(const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t r, AlignScratch &x, typename cplx_arg<CPLX>::type cp = typename cplx_arg<CPLX>::type()) {
   const uint32_t qlen = read_len(b, r);
   const CandHdr ch = b.ch[r];
   const ReadCtl ctl = b.ctl[r];
@@ -1561,9 +1586,10 @@ SMG_HD inline void stage_align(const Batch &b, const DevIndex &ix, const MapPar 
       tq1 = phase_clock(); aph[1] += tq1 - tq0; tq0 = tq1;
       int tb_dn = 0, tb_qs = 0, tb_rs = 0;
       bool tb_done = false;
+      int ccnt[CPLX_NCODES] = {0, 0, 0, 0, 0, 0};         // CPLX: diagonal steps of the traceback per reference letter
 #if defined(__HIP_DEVICE_COMPILE__)
       if (!nerr && !skip && max_scor >= minscore && tW == 0 && x.rows_form) {      // row-major directions: traceback by the wave, on the scalar unit
-        tb_dn = traceback_uniform(dtmp, dtmpcap, &tb_qs, &tb_rs, band, dirm, max_i, max_j, max_scor, q, win, (int)M[0], (int)M[1], gi, ge);
+        tb_dn = traceback_uniform<CPLX>(dtmp, dtmpcap, &tb_qs, &tb_rs, band, dirm, max_i, max_j, max_scor, q, win, (int)M[0], (int)M[1], gi, ge, CPLX ? ccnt : nullptr);
         tb_done = true;
       }
 #else
@@ -1575,19 +1601,32 @@ SMG_HD inline void stage_align(const Batch &b, const DevIndex &ix, const MapPar 
         if (!err && !skip && max_scor >= minscore) {
           int qs = tb_qs, rs = tb_rs;
           #if defined(__HIP_DEVICE_COMPILE__)
-          const int dn = tb_done ? tb_dn : traceback_scalar(dtmp, dtmpcap, &qs, &rs, band, dirm, max_i, max_j, max_scor, q, win, M, gi, ge, tW, &sg);
+          const int dn = tb_done ? tb_dn : traceback_scalar<CPLX>(dtmp, dtmpcap, &qs, &rs, band, dirm, max_i, max_j, max_scor, q, win, M, gi, ge, tW, &sg, CPLX ? ccnt : nullptr);
 #else
-          const int dn = traceback_scalar(dtmp, dtmpcap, &qs, &rs, band, dirm, max_i, max_j, max_scor, q, win, M, gi, ge, tW);
+          const int dn = traceback_scalar<CPLX>(dtmp, dtmpcap, &qs, &rs, band, dirm, max_i, max_j, max_scor, q, win, M, gi, ge, tW, nullptr, CPLX ? ccnt : nullptr);
 #endif
           if (dn < 0) { err = (dn == -2) ? SMG_ERR_CAP : (dn == -3 ? SMG_ERR_SCORE : SMG_ERR_ASSERT); x.state[S_SITE] = __LINE__; }
+          // the score the alignment carries from here on: weighted once the checksum test has passed (alignment.c:767-772)
+          int ali_scor = max_scor;
+          if constexpr (CPLX) {
+            if (!err) {
+              const int cr = cplx_scale(&ali_scor, max_scor, ccnt, cp.logtab, cp.nlog, cp.lambda);
+              if (cr) { err = cr == CPLX_EXCEEDS ? SMG_ERR_CPLX : SMG_ERR_ASSERT; x.state[S_SITE] = __LINE__; }
+            }
+          }
           const int qe = max_j, re = max_i;
+          if (CPLX && !err && !(qs + minscorlen > qe + 1) && ali_scor < minscore) {
+            // weighted below the threshold: not added, but the recursion into both remainders goes on as below (alignment.c:1384-1431)
+            if (s_right > re + minscorlen) { if (nsp >= 62) { err = SMG_ERR_CAP; x.state[S_SITE] = __LINE__; } else { x.ivstack[2 * nsp] = re + 1; x.ivstack[2 * nsp + 1] = s_right; nsp++; } }
+            if (!err && s_left + minscorlen < rs) { if (nsp >= 62) { err = SMG_ERR_CAP; x.state[S_SITE] = __LINE__; } else { x.ivstack[2 * nsp] = s_left; x.ivstack[2 * nsp + 1] = rs - 1; nsp++; } }
+          } else
           if (!err && !(qs + minscorlen > qe + 1)) {
             // addALIMETAtoRsltSet (alignment.c:1277): forward DiffStr appended to the scratch string pool
             const int nali = x.state[S_NALI];
             if ((uint32_t)(res_first + nali) >= x.rescap || (uint32_t)(x.state[S_NDSTR] + dn + 2) > x.dstrcap) { err = x.pass == 1 ? SMG_ERR_RETRY : SMG_ERR_CAP; x.state[S_SITE] = __LINE__; }   // the second pass has large result slots
             else {
               Result &a = x.res[res_first + nali];
-              a.swatscor = max_scor; a.q_start = (uint32_t)qs; a.q_end = (uint32_t)qe; a.s_start = (uint64_t)rs; a.s_end = (uint64_t)re;
+              a.swatscor = ali_scor; a.q_start = (uint32_t)qs; a.q_end = (uint32_t)qe; a.s_start = (uint64_t)rs; a.s_end = (uint64_t)re;
               a.stroffs = (uint32_t)x.state[S_NDSTR];
               const int fl = diffstr_reverse(x.dstr + a.stroffs, dtmp, dn);
               if (fl < 0) { err = SMG_ERR_ASSERT; x.state[S_SITE] = __LINE__; }
