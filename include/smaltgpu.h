@@ -149,6 +149,34 @@ int smaltgpu_index_build_device(smaltgpu_index **out, int device, const uint8_t 
                                 int64_t nseq, int32_t k, int32_t s, float *build_ms);
 int smaltgpu_index_save(const smaltgpu_index *ix, const char *prefix);
 
+/* ---- index construction from the text of a FASTA file (`smalt index <prefix> <reference.fa>`: seqSetAddFromFastqFile
+ * sequence.c:2391-2434 over seqFastqRead :1960-1990, readHeader :1056-1146 and readSeqFast :1229-1304, then buildHashIndex
+ * smalt.c:338-412).  `text[0..text_len)`: the whole file in host memory (inflated if it was compressed).  The text is copied to
+ * the device and parsed there (smg_fasta.hip); bases, offsets and names go to smaltgpu_index_build_device.  The rules are the
+ * reference's: a prompt counts only as the first byte of a line and not on the line behind a header line, every other byte of the
+ * sequence lines that is not white space is a base, the name of a sequence is its whole header line with each run of white space
+ * cut down to its first character.  SMALTGPU_EARG with a message that names the cause: an empty text, a text that does not
+ * begin with a prompt, a FASTQ-format reference ('@' or '+' prompts: the reference program takes those, this path does not), and
+ * what smaltgpu_index_build_device refuses (a sequence shorter than the word length, ...).  parse_ms / build_ms (may be NULL):
+ * device time of the parse and of the construction.  SMALTGPU_FASTA_BLOCK in the environment (read once per call; a test hook):
+ * bytes of text per workgroup, at least 64 (default 256 KiB); small values are for small texts: the block size is doubled
+ * until the text has at most 2^20 blocks. ---- */
+int smaltgpu_index_build_text(smaltgpu_index **out, int device, const char *text, uint64_t text_len, int32_t k, int32_t s, float *parse_ms,
+                              float *build_ms);
+/* The parse alone, back in host memory.  The view's arrays belong to `fa` and hold until smaltgpu_fasta_free. */
+typedef struct smaltgpu_fasta smaltgpu_fasta;
+typedef struct smaltgpu_fasta_view {
+  int64_t nseq;
+  const char *const *names;            /* nseq strings */
+  const uint64_t *seq_off;             /* nseq + 1 offsets into bases */
+  const uint8_t *bases;                /* the sequences concatenated, letters as in the file */
+  float upload_ms;                     /* host time of the copy of the text to the device */
+  float parse_ms;                      /* device time of the three steps together ... */
+  float step_ms[3];                    /* ... and of each: block summaries, their composition, the output pass */
+} smaltgpu_fasta_view;
+int smaltgpu_fasta_parse(smaltgpu_fasta **out, int device, const char *text, uint64_t text_len, smaltgpu_fasta_view *view);
+void smaltgpu_fasta_free(smaltgpu_fasta *fa);
+
 /* ---- mapper (replaces rmapCreate rmap.c:1511 / rmapDelete :1597) ---- */
 int smaltgpu_mapper_create(smaltgpu_mapper **out, const smaltgpu_index *ix, uint32_t max_batch_reads,
                            uint32_t max_read_len);

@@ -33,6 +33,11 @@ class IndexDesc(C.Structure):
                 ("packed", C.c_void_p), ("on_device", C.c_int32)]
 
 
+class FastaView(C.Structure):          # smaltgpu_fasta_view
+    _fields_ = [("nseq", C.c_int64), ("names", C.POINTER(C.c_char_p)), ("seq_off", C.POINTER(C.c_uint64)), ("bases", C.POINTER(C.c_uint8)),
+                ("upload_ms", C.c_float), ("parse_ms", C.c_float), ("step_ms", C.c_float * 3)]
+
+
 class Params(C.Structure):
     _fields_ = [("ktuple_maxhit", C.c_int32), ("min_cover", C.c_uint32), ("min_swatscor", C.c_int32),
                 ("min_swatscor_below_max", C.c_int32), ("min_basqval", C.c_int32), ("target_depth", C.c_int32),
@@ -137,6 +142,10 @@ def lib():
         L.smaltgpu_index_build_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_char_p), C.c_int64,
                                                   C.c_int32, C.c_int32, C.POINTER(C.c_float)]
         L.smaltgpu_index_save.argtypes = [C.c_void_p, C.c_char_p]
+        L.smaltgpu_index_build_text.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                                C.POINTER(C.c_float)]
+        L.smaltgpu_fasta_parse.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_uint64, C.POINTER(FastaView)]
+        L.smaltgpu_fasta_free.argtypes = [C.c_void_p]
         L.smaltgpu_index_info.argtypes = [C.c_void_p, C.POINTER(IndexDesc)]
         L.smaltgpu_params_default.argtypes = [C.POINTER(Params), C.c_void_p]
         L.smaltgpu_mapper_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32, C.c_uint32]
@@ -213,6 +222,34 @@ HIST_SAMPLED, HIST_SMOOTHED, HIST_SECTION = 0, 1, 2
 def sample_interval(npairs: int, every: int = 100) -> int:
     """Every how many pairs `smalt sample -u every` maps one (insSetSamplingInterval, insert.c:192-205)."""
     return lib().smaltgpu_sample_interval(npairs, every)
+
+
+def _fasta_text(path_or_bytes) -> bytes:
+    """the text of a FASTA file: bytes as they are, a path read whole (through gzip when the file is compressed)"""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return bytes(path_or_bytes)
+    with open(path_or_bytes, "rb") as f:
+        raw = f.read()
+    if raw[:2] == b"\x1f\x8b":
+        import gzip
+        raw = gzip.decompress(raw)
+    return raw
+
+
+def parse_fasta(path_or_bytes, device: int = 0):
+    """The reference sequences of a FASTA text as `smalt index` reads them, parsed on the device (smaltgpu_fasta_parse):
+    -> (names, sequences, times) with times = dict(upload_ms, parse_ms, step_ms).  Names are the whole header lines."""
+    text = _fasta_text(path_or_bytes)
+    h, v = C.c_void_p(), FastaView()
+    _check(lib().smaltgpu_fasta_parse(C.byref(h), device, text, len(text), C.byref(v)))
+    try:
+        names = [v.names[i].decode("latin-1") for i in range(v.nseq)]
+        base = C.addressof(v.bases.contents) if v.nseq else 0
+        seqs = [C.string_at(base + v.seq_off[i], v.seq_off[i + 1] - v.seq_off[i]) for i in range(v.nseq)]
+        times = dict(upload_ms=float(v.upload_ms), parse_ms=float(v.parse_ms), step_ms=[float(x) for x in v.step_ms])
+    finally:
+        lib().smaltgpu_fasta_free(h)
+    return names, seqs, times
 
 
 class InsertHistogram:
@@ -294,6 +331,19 @@ class Index:
         _check(lib().smaltgpu_index_build(C.byref(h), device, cat, off, nm, C.c_int64(len(seqs)), k, s, C.byref(ms)))
         ix = cls(h)
         ix.build_ms = float(ms.value)
+        return ix
+
+    @classmethod
+    def from_fasta(cls, path_or_bytes, k: int = 13, s: int = 6, device: int = 0) -> "Index":
+        """Build the index image from the text of a FASTA file (`smalt index`): a path (plain or gzipped) or the text itself.
+        The text is parsed on the device by the reference's rules (smaltgpu_index_build_text); `parse_ms` and `build_ms` hold
+        the device times of the parse and of the construction."""
+        text = _fasta_text(path_or_bytes)
+        h = C.c_void_p()
+        pms, bms = C.c_float(0.0), C.c_float(0.0)
+        _check(lib().smaltgpu_index_build_text(C.byref(h), device, text, len(text), k, s, C.byref(pms), C.byref(bms)))
+        ix = cls(h)
+        ix.parse_ms, ix.build_ms = float(pms.value), float(bms.value)
         return ix
 
     @classmethod

@@ -16,6 +16,7 @@
 #include "smg_dump.hpp"
 #include "smg_indexfile.hpp"
 #include "smg_indexbuild.h"
+#include "smg_fasta.hpp"
 #include "smg_kernels.h"
 
 using namespace smg;
@@ -205,6 +206,63 @@ extern "C" int smaltgpu_index_build(smaltgpu_index **out, int device, const uint
   (void)hipFree(d);
   return rv;
 }
+
+// ---- the same from the text of a FASTA file, parsed on the device (smg_fasta.hip) ----
+// bases in HBM (p->d_bases, the caller's), offsets, and the names cleaned on the host from the header lines the device found
+static int parse_fasta_text(int device, const char *text, uint64_t text_len, FastaParsed *p, std::vector<std::string> *names) {
+  if (!text && text_len) return fail(SMALTGPU_EARG, "null argument");
+  HIPCHK(hipSetDevice(device));
+  char err[256] = "";
+  if (fasta_parse_device(text, text_len, fa_block_bytes(getenv("SMALTGPU_FASTA_BLOCK")), p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
+  names->clear();
+  for (const uint64_t o : p->hdr_text_off) names->push_back(fa_clean_name(text + o + 1, (size_t)(text_len - o - 1)));
+  return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_index_build_text(smaltgpu_index **out, int device, const char *text, uint64_t text_len, int32_t k, int32_t s, float *parse_ms,
+                                         float *build_ms) {
+  if (!out) return fail(SMALTGPU_EARG, "null argument");
+  FastaParsed p;
+  std::vector<std::string> names;
+  int rv = parse_fasta_text(device, text, text_len, &p, &names);
+  if (rv) return rv;
+  std::vector<const char *> ptrs;
+  for (const std::string &x : names) ptrs.push_back(x.c_str());
+  rv = smaltgpu_index_build_device(out, device, p.d_bases, p.seq_off.data(), ptrs.data(), (int64_t)names.size(), k, s, build_ms);
+  (void)hipFree(p.d_bases);
+  if (!rv && parse_ms) *parse_ms = p.pass_a_ms + p.compose_ms + p.pass_b_ms;
+  return rv;
+}
+
+struct smaltgpu_fasta {
+  std::vector<std::string> names;
+  std::vector<const char *> name_ptrs;
+  std::vector<uint64_t> seq_off;
+  std::vector<uint8_t> bases;
+};
+
+extern "C" int smaltgpu_fasta_parse(smaltgpu_fasta **out, int device, const char *text, uint64_t text_len, smaltgpu_fasta_view *view) {
+  if (!out || !view) return fail(SMALTGPU_EARG, "null argument");
+  FastaParsed p;
+  smaltgpu_fasta *fa = new smaltgpu_fasta();
+  int rv = parse_fasta_text(device, text, text_len, &p, &fa->names);
+  if (!rv) {
+    fa->bases.resize((size_t)p.nbases + 1);
+    if (p.nbases && hipMemcpy(fa->bases.data(), p.d_bases, p.nbases, hipMemcpyDeviceToHost) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "copy of the parsed sequences to the host failed");
+    (void)hipFree(p.d_bases);
+  }
+  if (rv) { delete fa; return rv; }
+  fa->seq_off.swap(p.seq_off);
+  for (const std::string &x : fa->names) fa->name_ptrs.push_back(x.c_str());
+  memset(view, 0, sizeof(*view));
+  view->nseq = (int64_t)fa->names.size(); view->names = fa->name_ptrs.data(); view->seq_off = fa->seq_off.data(); view->bases = fa->bases.data();
+  view->upload_ms = p.upload_ms; view->step_ms[0] = p.pass_a_ms; view->step_ms[1] = p.compose_ms; view->step_ms[2] = p.pass_b_ms;
+  view->parse_ms = p.pass_a_ms + p.compose_ms + p.pass_b_ms;
+  *out = fa;
+  return SMALTGPU_OK;
+}
+
+extern "C" void smaltgpu_fasta_free(smaltgpu_fasta *fa) { delete fa; }
 
 // seqSetWriteBinFil (sequence.c:2448-2519) + hashTableWrite (hashidx.c:1214-1255) in the container of filio.c:48-77
 extern "C" int smaltgpu_index_save(const smaltgpu_index *ix, const char *prefix) {

@@ -10,6 +10,9 @@
 // mapper each and take blocks in turn (host copies of one block overlap the kernels of the other), the main thread
 // formats and writes the blocks in input order.
 //
+// `smaltgpu-map index` is `smalt index` (buildHashIndex, smalt.c:338-412): the text of the reference goes to the device whole,
+// smaltgpu_index_build_text parses it and builds the index there, smaltgpu_index_save writes the two files.
+//
 // `smaltgpu-map sample` is `smalt sample` (mapReads with MENU_SAMPLE, smalt.c:1395-1410): the pairs are counted in a pass of its
 // own, every n-th pair goes through the same stages, and the histogram of the insert sizes follows the SAM lines.
 #include <fcntl.h>
@@ -70,7 +73,12 @@ void usage() {
           "\n"
           "usage: smaltgpu-map sample [-m <int>] [-n <int>] [-o <file>] [-q <int>] [-u <int>] [-B <int>] [-g <list>] <index prefix> <reads> <mates>\n"
           "  `smalt sample`: maps every <u>-th pair (default 100; every (pairs / 4098)-th when that is fewer) and writes the SAM lines\n"
-          "  of these pairs, the sampled and the smoothed histogram of their insert sizes and the section that -I reads\n");
+          "  of these pairs, the sampled and the smoothed histogram of their insert sizes and the section that -I reads\n"
+          "\n"
+          "usage: smaltgpu-map index [-k <int>] [-s <int>] [-g <device>] <index prefix> <reference.fa>[.gz]\n"
+          "  `smalt index`: word length <k> (default 13) sampled every <s> bases (default 6); reads the FASTA file, builds the index on the\n"
+          "  device and writes <index prefix>.sma and <index prefix>.smi.  (The reference program takes <s> = <k> when -s is not given;\n"
+          "  give both options to get the same index from both programs.)\n");
   exit(2);
 }
 
@@ -136,7 +144,8 @@ struct Source {
     if (!gz) { *got = want < maplen - pos ? want : maplen - pos; *last = pos + *got >= maplen; return map + pos; }
     if (boff > (64u << 20) || (boff && boff == buf.size())) { buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)boff); boff = 0; }
     while (!gz_end && buf.size() - boff < want) {
-      const size_t old = buf.size(), add = want > (8u << 20) ? (size_t)want : (size_t)(8u << 20);
+      const uint64_t miss = want - (buf.size() - boff);                // a step of 8 MiB to 1 GiB: zlib counts the room in 32 bits
+      const size_t old = buf.size(), add = (size_t)(miss < (8u << 20) ? (8u << 20) : miss > (1u << 30) ? (1u << 30) : miss);
       buf.resize(old + add);
       zs.next_out = (Bytef *)buf.data() + old; zs.avail_out = (uInt)add;
       while (zs.avail_out && !gz_end) {
@@ -166,9 +175,56 @@ struct Source {
   bool done() const { return gz ? (gz_end && boff >= buf.size()) : pos >= maplen; }
 };
 
+// `smaltgpu-map index`: defaults as menu.c:597-598
+int index_main(int argc, char **argv) {
+  int k = 13, s = 6, device = 0, a = 2;
+  for (; a < argc && argv[a][0] == '-' && argv[a][1]; a++) {
+    const char o = argv[a][1];
+    if (argv[a][2] || !strchr("ksg", o) || a + 1 >= argc) usage();
+    char *end = nullptr;
+    const long v = strtol(argv[++a], &end, 10);
+    if (end == argv[a] || *end || v < -1000 || v > 1000) die("index: not a number", argv[a]);
+    if (o == 'k') k = (int)v; else if (o == 's') s = (int)v; else device = (int)v;
+  }
+  if (argc - a != 2) usage();
+  const std::string prefix = argv[a];
+  const char *fafil = argv[a + 1];
+  if (k < 3 || k > 20) die("index: -k out of range (3 .. 20)");                  // MENU_KMERLEN_MIN / _MAX, menu.c:595-596, checked at :1272
+  if (s < 1 || s > 127) die("index: -s out of range (1 .. 127)");                // the reference's check of -s, menu.c:1281
+  const auto t0 = std::chrono::steady_clock::now();
+  auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  Source src;
+  src.open(fafil);
+  const char *text = src.map;
+  uint64_t len = src.maplen;
+  if (src.gz) {                                                                  // the whole text, inflated
+    bool last = false;
+    for (uint64_t want = 64u << 20; !last; want *= 2) text = src.window(want, &len, &last);
+  }
+  fprintf(stderr, "# Reading sequences ... %llu bytes of text (%.0f ms)\n", (unsigned long long)len, ms());
+  smaltgpu_index *ix = nullptr;
+  float parse_ms = 0, build_ms = 0;
+  if (smaltgpu_index_build_text(&ix, device, text, len, k, s, &parse_ms, &build_ms)) die("index", smaltgpu_last_error());
+  const char *const *names; const uint64_t *sop; int64_t nseq;
+  if (smaltgpu_index_seqnames(ix, &names, &sop, &nseq)) die("index", smaltgpu_last_error());
+  fprintf(stderr, "# %lld sequences, %llu bases; word length = %d bases, skip step = %d bases; device: parse %.2f ms, construction %.2f ms (%.0f ms)\n",
+          (long long)nseq, (unsigned long long)sop[nseq], k, s, parse_ms, build_ms, ms());
+  src.close();
+  fprintf(stderr, "# Writing sequence set and table to file ...\n");
+  if (smaltgpu_index_save(ix, prefix.c_str())) {                                 // no file that looks like an index behind a failed run
+    const std::string why = smaltgpu_last_error();
+    (void)unlink((prefix + ".sma").c_str()); (void)unlink((prefix + ".smi").c_str());
+    die("index", why.c_str());
+  }
+  smaltgpu_index_free(ix);
+  fprintf(stderr, "# done (%.0f ms)\n", ms());
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+  if (argc > 1 && !strcmp(argv[1], "index")) return index_main(argc, argv);
   const bool sampling = argc > 1 && !strcmp(argv[1], "sample");
   const char *fmt = sampling ? "sam:nohead" : "cigar", *oufil = nullptr, *scorespec = nullptr, *histfil = nullptr;   // sample prints SAM lines without a header
   int m = -1, d = 0, seed = 0, q = 0, nthreads = 0, ins_max = 500, ins_min = 0, lib = SMALTGPU_LIB_PE, every = 100;    // -u: MENU_DEFAULTS_READSKIP (menu.c:618)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Index construction: smaltgpu_index_build_device on a synthetic reference resident in HBM against
 the reference's own single-threaded `smalt index` (oracle/_ref/smalt) on a bounded sample written to disk.
-Prints one JSON line.  Not part of the bench.py contract."""
+Prints one JSON line.  --fasta: the same reference written as a FASTA file and indexed from its text -- smaltgpu_index_build_text
+(upload, parse and construction times) and the whole `smaltgpu-map index` program -- beside the same `smalt index` sample; the
+result also goes to the file named by --out (default profiles/index_from_fasta.json).  Not part of the bench.py contract."""
 import argparse
 import json
 import os
@@ -16,8 +18,75 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def cpu_reference(ascii_ref, nsmp, k, s):
+    """seconds the reference's `smalt index` takes for the first nsmp bases written as one FASTA sequence (None: it failed)"""
+    smp = ascii_ref[:nsmp].cpu().numpy().tobytes()
+    smalt = os.path.join(ROOT, "oracle", "_ref", "smalt")
+    with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
+        fa = os.path.join(tmp, "s.fa")
+        with open(fa, "wb") as f:
+            f.write(b">chr1\n")
+            for o in range(0, nsmp, 60):
+                f.write(smp[o:o + 60] + b"\n")
+        t = time.time()
+        r = subprocess.run([smalt, "index", "-k", str(k), "-s", str(s), os.path.join(tmp, "s"), fa], capture_output=True)
+        return time.time() - t if r.returncode == 0 else None
+
+
+def fasta_mode(a, ref, ascii_ref, sop, names):
+    """index from the text of a FASTA file: library call and whole program"""
+    import hashlib
+    from smalt_amd import api, synth
+    tot = sop[-1]
+    md5 = lambda p: hashlib.md5(open(p, "rb").read()).hexdigest()  # noqa: E731
+    with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
+        fa = os.path.join(tmp, "ref.fa")
+        codes = ref.cpu().numpy()
+        synth.write_fasta(fa, [codes[sop[i]:sop[i + 1]] for i in range(len(names))])
+        t = time.time()
+        text = open(fa, "rb").read()
+        read_s = time.time() - t
+        runs = []
+        for _ in range(a.reps):
+            t = time.time()
+            ix = api.Index.from_fasta(text, a.k, a.s, 0)
+            runs.append(dict(wall_ms=(time.time() - t) * 1e3, parse_ms=ix.parse_ms, build_ms=ix.build_ms))
+            ix.close()
+        _, _, times = api.parse_fasta(text, 0)                    # upload time and the share of each step
+        want = os.path.join(tmp, "want")
+        ix = api.Index.build_device(ascii_ref.data_ptr(), sop, names, a.k, a.s, 0)
+        ix.save(want)
+        ix.close()
+        prog = []
+        pre = os.path.join(tmp, "prog")
+        for _ in range(a.reps):
+            t = time.time()
+            r = subprocess.run([os.path.join(ROOT, "smalt_amd", "smaltgpu-map"), "index", "-k", str(a.k), "-s", str(a.s), pre, fa], capture_output=True)
+            prog.append(time.time() - t)
+            assert r.returncode == 0, r.stderr.decode()[-2000:]
+        same = md5(pre + ".sma") == md5(want + ".sma") and md5(pre + ".smi") == md5(want + ".smi")
+        stderr_last = r.stderr.decode().strip().split("\n")
+    nsmp = min(int(a.cpu_mbp * 1e6), tot)
+    cpu_s = cpu_reference(ascii_ref, nsmp, a.k, a.s)
+    best = min(runs, key=lambda x: x["wall_ms"])
+    out = {"what": "index from the text of a FASTA file (smaltgpu_index_build_text, smaltgpu-map index)", "bases": tot, "text_bytes": len(text), "k": a.k, "s": a.s,
+           "file_read_s": read_s, "library": {"runs": runs, "best": best, "upload_ms": times["upload_ms"], "parse_ms": times["parse_ms"],
+                                              "parse_steps_ms": dict(zip(("block_summaries", "compose", "output_pass"), times["step_ms"])),
+                                              "parse_text_GBps": len(text) / (times["parse_ms"] / 1e3) / 1e9},
+           "program": {"wall_s": prog, "best_wall_s": min(prog), "bases_per_s": tot / min(prog), "files_equal_build_device": same, "progress": stderr_last},
+           "cpu_reference": {"kind": "reference", "what": "`smalt index` (one thread, FASTA parse included)", "sample_bases": nsmp, "seconds": cpu_s,
+                             "bases_per_s": (nsmp / cpu_s) if cpu_s else None},
+           "program_speedup_per_base": (tot / min(prog)) / (nsmp / cpu_s) if cpu_s else None}
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(json.dumps(out) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fasta", action="store_true", help="index from the text of a FASTA file (library call and `smaltgpu-map index`)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "index_from_fasta.json"), help="--fasta: file the result is written to")
     ap.add_argument("--nchr", type=int, default=24)
     ap.add_argument("--chr-mbp", type=float, default=125.0)
     ap.add_argument("-k", type=int, default=13)
@@ -35,6 +104,8 @@ def main():
     sop = [i * chrlen for i in range(a.nchr + 1)]
     names = ["chr%d" % (i + 1) for i in range(a.nchr)]
     tot = sop[-1]
+    if a.fasta:
+        return fasta_mode(a, ref, ascii_ref, sop, names)
     times = []
     info = None
     for _ in range(a.reps):
@@ -59,19 +130,7 @@ def main():
         torch_ms = None
     # CPU reference on a bounded sample
     nsmp = int(a.cpu_mbp * 1e6)
-    smp = ascii_ref[:nsmp].cpu().numpy().tobytes()
-    smalt = os.path.join(ROOT, "oracle", "_ref", "smalt")
-    cpu_s = None
-    with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
-        fa = os.path.join(tmp, "s.fa")
-        with open(fa, "wb") as f:
-            f.write(b">chr1\n")
-            for o in range(0, nsmp, 60):
-                f.write(smp[o:o + 60] + b"\n")
-        t = time.time()
-        r = subprocess.run([smalt, "index", "-k", str(a.k), "-s", str(a.s), os.path.join(tmp, "s"), fa], capture_output=True)
-        if r.returncode == 0:
-            cpu_s = time.time() - t
+    cpu_s = cpu_reference(ascii_ref, nsmp, a.k, a.s)
     ntup = (tot + a.s - 1) // a.s
     # algorithmic HBM bytes of the construction (PERFECT, 32-bit keys): every base read twice (packing, k-mer words) and
     # 0.4 B/base of packed words written; per sampled k-mer the (key, serial) pair written once (8 B) and read + written by
