@@ -382,6 +382,7 @@ struct smaltgpu_mapper {
   uint8_t *cand_scr_dbg = nullptr; uint32_t cand_dbg_reads = 0;
   int *sw_rows = nullptr; uint32_t sw_rowlen = 0, sw_threads = 0;
   void *strip_bnd = nullptr; uint8_t *strip_win = nullptr; uint32_t strip_grid = 0;   // k_sw_strip: boundary columns + decoded window per workgroup
+  uint32_t full_grid = 8192;                          // workgroups (one wave each) of the register-tiled K2a kernels
   uint8_t *align_scr = nullptr; size_t align_bytes = 0; uint32_t align_slots = 0;
   uint8_t *align_scr2 = nullptr; size_t align_bytes2 = 0; uint32_t align_slots2 = 0; uint64_t dircap2 = 0;   // second K3 pass: few slots with full-size direction matrices
   uint32_t wincap = 0, rescap_slot = 0, dstrcap_slot = 0; uint64_t dircap = 0;
@@ -636,6 +637,8 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
     m->wincap = 4 * m->qmax + 1024;
     m->strip_grid = 5120;                              // workgroups (one wave each) of the strip kernels: five per SIMD (96 registers); 2048: 5.2, 4096: 6.0, 5120: 6.2 TCUPS at 8 kbp
     if (const char *e = getenv("SMALTGPU_STRIP_GRID")) { const long v = atol(e); if (v >= 64 && v <= 16384) m->strip_grid = (uint32_t)v; }   // tuning hook
+    // tuning hook; with a few workgroups a wave meets the same read in successive iterations even on a small batch (tests/test_gpu_sw_prologue.py)
+    if (const char *e = getenv("SMALTGPU_SWFULL_GRID")) { const long v = atol(e); if (v >= 1 && v <= 16384) m->full_grid = (uint32_t)v; }
     if ((uint64_t)m->strip_grid * m->wincap * 18 > (8ull << 30)) m->strip_grid = (uint32_t)((8ull << 30) / ((uint64_t)m->wincap * 18));
     if (!rv) rv = dalloc((uint8_t **)&m->strip_bnd, (size_t)m->strip_grid * 2 * m->wincap * 8);
     DA(m->strip_win, (size_t)m->strip_grid * m->wincap * 2);      // code pairs of the packed strip kernel
@@ -772,7 +775,7 @@ static int run_pipeline(smaltgpu_mapper *m, const uint8_t *d_bases, const uint8_
   { CandGeom g = cgeom; g.ngrp = ngrp; g.debug = slot_per_read; if (!two_pass) g.pass = 0; if (!rv) rv = launch_cands(s, b, d, p, cscr, cslots, g); }
   if (two_pass) { CandGeom g = m->cg2; g.ngrp = ngrp; g.debug = 0; g.pass = 2; if (!rv) rv = launch_cands(s, b, d, p, m->cand_scr2, m->cand_slots2, g); }
   HIPCHK(hipEventRecord(m->ev[T_SW_FULL], s));
-  if (!rv) rv = launch_sw_full(s, b, d, p, m->max_len, b.rccap, 8192);
+  if (!rv) rv = launch_sw_full(s, b, d, p, m->max_len, b.rccap, m->full_grid);
   HIPCHK(hipEventRecord(m->ev[T_SW_SCALAR], s));
   if (!rv) rv = launch_sw_strip(s, b, d, p, m->strip_bnd, m->strip_win, m->wincap, m->strip_grid);
   if (!rv) rv = launch_sw_scalar(s, b, d, p, m->sw_rows, m->sw_rowlen, m->sw_threads, m->max_len);

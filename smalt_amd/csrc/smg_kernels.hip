@@ -558,6 +558,132 @@ __device__ inline void sw16_rowtab2(uint2 *rowtab2, const Sw16Par &sp) {
 }
 enum : uint32_t { SW16_NPAIR = 5u | (5u << 3) };
 
+// ---------------------------------------------------------------------------------------
+// What the packed sweep is handed -- the selectors of the read's columns and the code pairs of the window's rows -- is
+// put together from whole words:
+//  * the codes of a read go through LDS once per read (both strands, one coalesced load by the whole wave, padded with
+//    the selector of the constant 0 beyond the read); a lane takes its C columns as dwords and one v_perm per column
+//    makes the selector.  Consecutive ranked candidates belong to one read, so the tasks of a wave iteration nearly
+//    always share it (and a wave whose next iteration is still in that read keeps it);
+//  * a lane decodes ten window entries at a time from two adjacent words of the packed reference (ten bases each), all
+//    ten codes at once in their 3-bit fields.
+// ---------------------------------------------------------------------------------------
+template <int G, int C>
+struct Sw16Geo {
+  enum : int { CP = (C + 3) & ~3,      // bytes that the C columns of a lane take in the staged read: whole dwords
+               NW = CP / 4, QST = G * CP };
+};
+typedef uint32_t __attribute__((may_alias)) u32_alias;
+enum : uint32_t { SW16_PAD4 = 0x0c0c0c0cu, SW16_N10 = 0x2DB6DB6Du /* ten codes 5 */ };
+// entries of a group's window array: rows -(G-1) .. WMAX+G-2, in whole runs of ten
+constexpr int sw16_went(int G, int WMAX) { return (WMAX + 2 * G - 2 + 9) / 10 * 10; }
+
+// Selector bytes of one read, both strands, to qst[2][G * CP]: column j = gg * C + cc at byte gg * CP + cc; the code
+// below the read's length, 0x0c (the constant 0 of v_perm) from there on.  RAW: codes as the test entry passes them
+// (3 bits, one array for both); returns whether the read has a code beyond ACGT.
+template <int G, int C, bool RAW>
+__device__ inline bool sw16_stage(uint8_t *qst, const uint8_t *fw, const uint8_t *rc, uint32_t qlen) {
+  constexpr uint32_t CP = Sw16Geo<G, C>::CP, QST = Sw16Geo<G, C>::QST;
+  bool bad = false;
+  for (uint32_t t = threadIdx.x; t < QST; t += 64) {
+    const uint32_t gg = t / CP, cc = t % CP, j = gg * (uint32_t)C + cc;
+    uint32_t a = 0x0cu, r = 0x0cu;
+    if (cc < (uint32_t)C && j < qlen) {
+      a = fw[j];
+      if (RAW) { bad = bad || (a & 7u) >= 4u; a &= 3u; r = a; }
+      else r = rc[j];
+    }
+    qst[t] = (uint8_t)a; qst[QST + t] = (uint8_t)r;
+  }
+  return RAW && __any(bad);
+}
+// the C selector bytes of lane g from the staged read
+template <int G, int C, int NW>
+__device__ inline void sw16_fetch(uint32_t (&x)[NW], const uint8_t *qst, int g, bool rev) {
+  const u32_alias *src = (const u32_alias *)(qst + (rev ? (int)Sw16Geo<G, C>::QST : 0) + g * (int)Sw16Geo<G, C>::CP);
+#pragma unroll
+  for (int w = 0; w < NW; w++) x[w] = src[w];
+}
+// sel[cc]: selector bytes {qA, 4 + qB} of column cc next to two bytes 0x0c (half floats: the score byte is the high byte)
+template <int G, int C, int NW>
+__device__ inline void sw16_sel(uint32_t (&sel)[C], const uint32_t (&xa)[NW], const uint32_t (&xb)[NW], int fp) {
+  uint32_t xh[NW];
+#pragma unroll
+  for (int w = 0; w < NW; w++) xh[w] = xb[w] + 0x04040404u - ((xb[w] & 0x08080808u) >> 1);     // + 4 on the codes, 0x0c stays
+  if (fp) {
+#pragma unroll
+    for (int cc = 0; cc < C; cc++) {
+      const uint32_t t = (uint32_t)(cc & 3);
+      sel[cc] = __builtin_amdgcn_perm(xh[cc >> 2], xa[cc >> 2], 0x000c000cu | (t << 8) | ((4u + t) << 24)) | 0x000c000cu;
+    }
+  } else {
+#pragma unroll
+    for (int cc = 0; cc < C; cc++) {
+      const uint32_t t = (uint32_t)(cc & 3);
+      sel[cc] = __builtin_amdgcn_perm(xh[cc >> 2], xa[cc >> 2], 0x0c000c00u | t | ((4u + t) << 16)) | 0x0c000c00u;
+    }
+  }
+}
+
+// Entry 0 of a task's window array (row -(G-1)) is base s of word wbase of ix.packed; wbase may lie before word 0.
+template <int G>
+__device__ inline void sw16_win_origin(uint64_t gbase, bool small, int64_t &wbase, uint32_t &s) {
+  uint64_t w0; uint32_t r0;
+  if (small) { const uint32_t p32 = (uint32_t)gbase, w = p32 / 10u; w0 = w; r0 = p32 - w * 10u; }     // wave-uniform choice: a multiply-high
+  else { w0 = gbase / 10; r0 = (uint32_t)(gbase - w0 * 10); }
+  const uint32_t a = r0 + 20u - (uint32_t)(G - 1), qq = a / 10u;
+  s = a - qq * 10u;
+  wbase = (int64_t)w0 - 2 + (int64_t)qq;
+}
+// ten packed codes at once: 7 -> A (0), 4, 5, 6 -> N (5)
+__device__ inline uint32_t sw16_map10(uint32_t w) {
+  const uint32_t b2 = w & 0x24924924u;                       // bit 2 of every code
+  const uint32_t is7 = b2 & (w << 1) & (w << 2);
+  const uint32_t isn = b2 ^ is7;
+  const uint32_t full = b2 | (b2 >> 1) | (b2 >> 2);
+  return (w & ~full) | isn | (isn >> 2);
+}
+// codes of entries 10 m .. 10 m + 9 of one task (entry d in bits 3 (9 - d)); rows outside the window are N
+// (words wbase + m and the next one, both kept inside the packed array: mlo, mhi are the task's bounds of m for that)
+template <int G>
+__device__ inline uint32_t sw16_codes10(const uint32_t *packed, int64_t wbase, uint32_t s, uint32_t m, uint32_t mlo, uint32_t mhi, uint32_t wlen) {
+  const uint32_t ka = min(max(m, mlo), mhi), kb = min(max(m + 1u, mlo), mhi);
+  const uint32_t *pw = packed + wbase;
+  const uint32_t hi = pw[ka] & 0x3fffffffu, lo = pw[kb] & 0x3fffffffu;
+  const uint64_t cat = ((uint64_t)hi << 30) | lo;
+  const uint32_t raw = (uint32_t)(cat >> (3u * (10u - s))) & 0x3fffffffu;
+  const int i0 = (int)(10u * m) - (G - 1);                   // row of entry 10 m
+  int dlo = -i0, dhi = (int)wlen - i0;
+  dlo = dlo < 0 ? 0 : (dlo > 10 ? 10 : dlo);
+  dhi = dhi < 0 ? 0 : (dhi > 10 ? 10 : dhi);
+  const uint32_t valid = ((1u << (3 * (10 - dlo))) - 1u) & ~((1u << (3 * (10 - dhi))) - 1u);
+  return (sw16_map10(raw) & valid) | (SW16_N10 & ~valid);
+}
+// the window array of a lane group: entry e = row e - (G-1) as code of task A | code of task B << 3, N pairs around the windows
+template <int G>
+__device__ inline void sw16_window(uint16_t *wrow, int g, uint32_t nent, const uint32_t *packed, int64_t lastw, const int64_t (&wbase)[2],
+                                   const uint32_t (&ws)[2], const uint32_t (&wlen)[2]) {
+  u32_alias *dst = (u32_alias *)wrow;
+  const uint32_t nchunk = (nent + 9u) / 10u;
+  uint32_t mlo[2], mhi[2];
+#pragma unroll
+  for (int u = 0; u < 2; u++) {                               // wbase >= -2 and wbase <= lastw
+    const int64_t room = lastw - wbase[u];
+    mlo[u] = wbase[u] < 0 ? (uint32_t)(-wbase[u]) : 0u;
+    mhi[u] = room > 0x7fffffff ? 0x7fffffffu : (uint32_t)room;
+  }
+  for (uint32_t m = (uint32_t)g; m < nchunk; m += G) {
+    const uint32_t ma = sw16_codes10<G>(packed, wbase[0], ws[0], m, mlo[0], mhi[0], wlen[0]);
+    const uint32_t mb = sw16_codes10<G>(packed, wbase[1], ws[1], m, mlo[1], mhi[1], wlen[1]);
+#pragma unroll
+    for (int pr = 0; pr < 5; pr++) {
+      const int s0 = 3 * (9 - 2 * pr), s1 = s0 - 3;
+      const uint32_t e0 = ((ma >> s0) & 7u) | (((mb >> s0) & 7u) << 3), e1 = ((ma >> s1) & 7u) | (((mb >> s1) & 7u) << 3);
+      dst[5 * m + (uint32_t)pr] = e0 | (e1 << 16);
+    }
+  }
+}
+
 template <int G, int C, int WMAX>
 __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p, uint32_t ntask_cap) {
   // the small-LDS instance (WMAX = SW_SHORT_WMAX) runs first; the large one only sees what is left
@@ -565,91 +691,86 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
   const unsigned long long nlong = WMAX > SW_SHORT_WMAX ? b.work[WK_LONG_TASKS] : 0;
   if (WMAX > SW_SHORT_WMAX && nlong == 0) return;
   const uint32_t *list = (WMAX > SW_SHORT_WMAX && b.long_list && nlong <= b.long_cap) ? b.long_list : nullptr;
-  constexpr int NG = 64 / G;
-  __shared__ uint16_t win[NG][WMAX + 2 * G];
+  constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
+  __shared__ __attribute__((aligned(16))) uint16_t win[NG][sw16_went(G, WMAX)];
   __shared__ uint2 rowtab2[64];
+  __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t ntask = list ? (uint32_t)nlong : min(*b.rc_count, ntask_cap), npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
   sw16_rowtab2(rowtab2, sp);
-  const uint32_t ngroups = gridDim.x * NG;
+  const uint32_t niter = (npair + NG - 1) / NG;                             // iterations of NG task pairs, dealt to the waves in turn
+  const bool small = ix.totlen <= 0xffffffffull;
+  const int64_t lastw = (int64_t)(ix.totlen / 10);
+  uint32_t staged = 0xffffffffu;                                           // read whose codes are in qst
   unsigned long long cells = 0, ntasks_done = 0;
-  for (uint32_t t0 = blockIdx.x * NG; t0 < npair; t0 += ngroups) {
-    const uint32_t tp = t0 + grp;
-    RCand c[2];
-    bool live[2] = {false, false};
-    uint32_t qlen[2] = {0, 0}, wlen[2] = {0, 0}, tix[2] = {0, 0};
-    uint64_t gbase[2] = {0, 0};
-    const uint8_t *q[2] = {b.codes, b.codes};
+  for (uint32_t it = blockIdx.x; it < niter; it += gridDim.x) {
+    const uint32_t tp = it * NG + grp;
+    // lanes 0 and 1 of a group read the records of its two tasks and hand the others what they need
+    uint32_t tix = 0, flags = 0, rid = 0, meta = 0, wlo = 0, whi = 0;
+    {
+      const uint32_t tl = 2 * tp + (uint32_t)g;
+      if (g < 2 && tp < npair && tl < ntask) {
+        tix = list ? list[tl] : tl;
+        const RCand *rc = b.rcpool + tix;
+        flags = rc->flags;
+        const uint32_t r = rc->rid;
+        const uint64_t rs = rc->rs;
+        const uint32_t ql = read_len(b, r), wl = (uint32_t)(rc->re - rs + 1);
+        if (!(flags & (RCF_BANDED | RCF_ERR | RCF_QN | RCF_SCORED)) && wl <= (uint32_t)WMAX && ql <= (uint32_t)(G * C)) {
+          const int32_t sq = rc->sqidx;
+          int64_t wb; uint32_t s;
+          sw16_win_origin<G>((sq < 0 ? 0ull : ix.sop[sq]) + rs, small, wb, s);
+          rid = r; wlo = (uint32_t)(uint64_t)wb; whi = (uint32_t)((uint64_t)wb >> 32);
+          meta = ql | (wl << 10) | (s << 20) | ((flags & RCF_REVERSE) ? 1u << 24 : 0u) | (1u << 25);
+        }
+      }
+    }
+    uint32_t qlen[2], wlen[2], ws[2], key[2];
+    int64_t wbase[2];
+    bool live[2], rev[2];
 #pragma unroll
     for (int u = 0; u < 2; u++) {
-      const uint32_t tl = 2 * tp + (uint32_t)u;
-      if (tp < npair && tl < ntask) {
-        tix[u] = list ? list[tl] : tl;
-        c[u] = b.rcpool[tix[u]];
-        qlen[u] = read_len(b, c[u].rid);
-        wlen[u] = (uint32_t)(c[u].re - c[u].rs + 1);
-        live[u] = !(c[u].flags & (RCF_BANDED | RCF_ERR | RCF_QN | RCF_SCORED)) && wlen[u] <= (uint32_t)WMAX && qlen[u] <= (uint32_t)(G * C);
-        gbase[u] = (c[u].sqidx < 0 ? 0ull : ix.sop[c[u].sqidx]) + c[u].rs;
-        q[u] = ((c[u].flags & RCF_REVERSE) ? b.codes_rc : b.codes) + b.read_off[c[u].rid];
-      }
-      if (!live[u]) { qlen[u] = 0; wlen[u] = 0; }
+      const int src = (lane & ~(G - 1)) + u;
+      const uint32_t mt = (uint32_t)__shfl((int)meta, src);
+      key[u] = (uint32_t)__shfl((int)rid, src);
+      wbase[u] = (int64_t)(((uint64_t)(uint32_t)__shfl((int)whi, src) << 32) | (uint32_t)__shfl((int)wlo, src));
+      qlen[u] = mt & 0x3ffu; wlen[u] = (mt >> 10) & 0x3ffu; ws[u] = (mt >> 20) & 0xfu; rev[u] = (mt >> 24) & 1u; live[u] = (mt >> 25) & 1u;
     }
     const uint32_t wmax = wlen[0] > wlen[1] ? wlen[0] : wlen[1];
     int nstep = (int)wmax + G - 1;
     for (int o = 32; o > 0; o >>= 1) nstep = max(nstep, __shfl_xor(nstep, o));
     nstep = __builtin_amdgcn_readfirstlane(nstep);                         // wave-uniform: a scalar loop bound for the sweep
-    {
-      // entry e = row e - (G - 1); N pairs around the window.  Every lane decodes a run of consecutive entries: one
-      // division per task to find the first packed word (10 bases per word), then shifts; the next word is loaded ahead.
-      const uint32_t nent = (uint32_t)(nstep + G - 1), per = (nent + G - 1) / G;
-      const uint32_t e0 = (uint32_t)g * per, e1 = e0 + per < nent ? e0 + per : nent;
-      const uint64_t lastw = ix.totlen / 10;
-      uint64_t wi[2] = {0, 0};
-      uint32_t wd[2] = {0, 0}, nx[2] = {0, 0}, off[2] = {0, 0};
+    sw16_window<G>(win[grp], g, (uint32_t)(nstep + G - 1), ix.packed, lastw, wbase, ws, wlen);
+    // selectors: one pass per distinct read among the wave's tasks (nearly always one, and often the read staged already)
+    uint32_t xa[NW], xb[NW];
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int i0 = (int)e0 - (G - 1);
-        const uint64_t pos = gbase[u] + (uint64_t)(i0 > 0 ? i0 : 0);
-        wi[u] = pos / 10; off[u] = (uint32_t)(pos - wi[u] * 10);
-        if (wlen[u] && e0 < e1) { wd[u] = ix.packed[wi[u] < lastw ? wi[u] : lastw]; nx[u] = ix.packed[wi[u] + 1 < lastw ? wi[u] + 1 : lastw]; }
+    for (int w = 0; w < NW; w++) { xa[w] = SW16_PAD4; xb[w] = SW16_PAD4; }
+    bool pend0 = live[0], pend1 = live[1];
+    for (;;) {
+      const unsigned long long pm = __ballot(pend0 || pend1);
+      if (!pm) break;
+      const uint32_t R = (uint32_t)__builtin_amdgcn_readlane((int)(pend0 ? key[0] : key[1]), __ffsll(pm) - 1);
+      if (R != staged) {
+        __syncthreads();
+        const uint64_t o = b.read_off[R];
+        sw16_stage<G, C, false>(qst, b.codes + o, b.codes_rc + o, (uint32_t)(b.read_off[R + 1] - o));
+        staged = R;
+        __syncthreads();
       }
-      for (uint32_t e = e0; e < e1; e++) {
-        const uint32_t i = e - (uint32_t)(G - 1);                         // (wraps for the leading pad: fails both tests below)
-        uint32_t cd[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-          cd[u] = 5u;
-          if (i < wlen[u]) {
-            const uint32_t c = (wd[u] >> (3 * (9 - off[u]))) & 7u;
-            cd[u] = (c == 7) ? 0u : ((c == 6 || c == 4) ? 5u : c);
-            if (++off[u] == 10) { off[u] = 0; wi[u]++; wd[u] = nx[u]; nx[u] = ix.packed[wi[u] + 1 < lastw ? wi[u] + 1 : lastw]; }
-          }
-        }
-        win[grp][e] = (uint16_t)(cd[0] | (cd[1] << 3));
-      }
+      if (pend0 && key[0] == R) { sw16_fetch<G, C>(xa, qst, g, rev[0]); pend0 = false; }
+      if (pend1 && key[1] == R) { sw16_fetch<G, C>(xb, qst, g, rev[1]); pend1 = false; }
     }
     uint32_t sel[C];
-#pragma unroll
-    for (int cc = 0; cc < C; cc++) {
-      const uint32_t j = (uint32_t)(g * C + cc);
-      const uint32_t sa = j < qlen[0] ? (uint32_t)q[0][j] : 0x0cu, sb = j < qlen[1] ? 4u + (uint32_t)q[1][j] : 0x0cu;
-      sel[cc] = sp.fp ? (0x000c000cu | (sa << 8) | (sb << 24)) : (0x0c000c00u | sa | (sb << 16));      // half floats: the score byte is the high byte
-    }
+    sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
     const uint32_t bb = sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
-    if (g == 0) {
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        if (live[u]) {
-          const int best = (int)((bb >> (16 * u)) & 0xffffu);
-          const uint32_t t = tix[u];
-          b.rcpool[t].swscor = best;
-          b.rcpool[t].flags = c[u].flags | RCF_SCORED | (best >= 65535 ? RCF_BANDED : 0u);   // ERRCODE_SWATEXCEED -> K2b
-          cells += (unsigned long long)qlen[u] * wlen[u];
-          ntasks_done += best < 65535 ? 1 : 0;      /* a score that left 16 bits waits for K2b */
-        }
-      }
+    if ((meta >> 25) & 1u) {                                               // lanes 0 and 1 with a task of their own that was scored
+      const int best = (int)((bb >> (16 * g)) & 0xffffu);
+      b.rcpool[tix].swscor = best;
+      b.rcpool[tix].flags = flags | RCF_SCORED | (best >= 65535 ? RCF_BANDED : 0u);   // ERRCODE_SWATEXCEED -> K2b
+      cells += (unsigned long long)(meta & 0x3ffu) * ((meta >> 10) & 0x3ffu);
+      ntasks_done += best < 65535 ? 1 : 0;      /* a score that left 16 bits waits for K2b */
     }
     __syncthreads();
   }
@@ -657,14 +778,16 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
   if (lane == 0 && cells) { atomicAdd(b.work + WK_CELLS_FULL, cells); atomicAdd(b.work + WK_TASKS_FULL, ntasks_done); }
 }
 
-// stand-alone form over explicit code arrays (tasks with non-ACGT query codes report -2: not handled here)
+// stand-alone form over explicit code arrays (tasks with non-ACGT query codes report -2: not handled here); every task
+// brings a query of its own, so the selectors take one staging pass per task
 template <int G, int C>
 __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
                                                        const uint32_t *r_off, uint32_t ntask, MapPar p, int32_t *scores) {
-  constexpr int NG = 64 / G;
+  constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
   constexpr int WMAX = SW_FULL_WMAX;
   __shared__ uint16_t win[NG][WMAX + 2 * G];
   __shared__ uint2 rowtab2[64];
+  __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
@@ -673,14 +796,14 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
   for (uint32_t t0 = blockIdx.x * NG; t0 < npair; t0 += ngroups) {
     const uint32_t tp = t0 + grp;
     bool live[2] = {false, false};
-    uint32_t qlen[2] = {0, 0}, wlen[2] = {0, 0};
-    const uint8_t *q[2] = {qcodes, qcodes}, *r[2] = {rcodes, rcodes};
+    uint32_t qlen[2] = {0, 0}, wlen[2] = {0, 0}, key[2] = {0, 0};
+    const uint8_t *r[2] = {rcodes, rcodes};
 #pragma unroll
     for (int u = 0; u < 2; u++) {
       const uint32_t t = 2 * tp + (uint32_t)u;
       if (tp < npair && t < ntask) {
         qlen[u] = q_off[t + 1] - q_off[t]; wlen[u] = r_off[t + 1] - r_off[t];
-        q[u] += q_off[t]; r[u] += r_off[t];
+        r[u] += r_off[t]; key[u] = t;
         live[u] = wlen[u] <= (uint32_t)WMAX && qlen[u] <= (uint32_t)(G * C);
       }
       if (!live[u]) { qlen[u] = 0; wlen[u] = 0; }
@@ -696,22 +819,24 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
       for (int u = 0; u < 2; u++) { const uint32_t x = i < wlen[u] ? (r[u][i] & 7u) : 5u; cd[u] = x == 7 ? 0 : ((x == 6 || x == 4) ? 5 : x); }
       win[grp][e] = (uint16_t)(cd[0] | (cd[1] << 3));
     }
-    uint32_t sel[C];
+    uint32_t xa[NW], xb[NW];
+#pragma unroll
+    for (int w = 0; w < NW; w++) { xa[w] = SW16_PAD4; xb[w] = SW16_PAD4; }
     bool qn[2] = {false, false};
-#pragma unroll
-    for (int cc = 0; cc < C; cc++) {
-      const uint32_t j = (uint32_t)(g * C + cc);
-      uint32_t s2[2];
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const uint32_t qc = j < qlen[u] ? (q[u][j] & 7u) : 0x0cu;
-        if (j < qlen[u] && qc >= 4) qn[u] = true;
-        s2[u] = qc == 0x0cu ? 0x0cu : (uint32_t)(4 * u) + (qc & 3u);
-      }
-      sel[cc] = sp.fp ? (0x000c000cu | (s2[0] << 8) | (s2[1] << 24)) : (0x0c000c00u | s2[0] | (s2[1] << 16));
+    bool pend0 = live[0], pend1 = live[1];
+    for (;;) {
+      const unsigned long long pm = __ballot(pend0 || pend1);
+      if (!pm) break;
+      const uint32_t R = (uint32_t)__builtin_amdgcn_readlane((int)(pend0 ? key[0] : key[1]), __ffsll(pm) - 1);
+      __syncthreads();
+      const uint32_t o = q_off[R];
+      const bool bad = sw16_stage<G, C, true>(qst, qcodes + o, qcodes + o, q_off[R + 1] - o);
+      __syncthreads();
+      if (pend0 && key[0] == R) { sw16_fetch<G, C>(xa, qst, g, false); qn[0] = bad; pend0 = false; }
+      if (pend1 && key[1] == R) { sw16_fetch<G, C>(xb, qst, g, false); qn[1] = bad; pend1 = false; }
     }
-#pragma unroll
-    for (int u = 0; u < 2; u++) for (int o = G / 2; o > 0; o >>= 1) { const int other = __shfl_xor((int)qn[u], o); qn[u] = qn[u] || other != 0; }
+    uint32_t sel[C];
+    sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
     const uint32_t bb = sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
     if (g == 0) {
