@@ -497,6 +497,11 @@ long smaltgpu_dump_read(smaltgpu_mapper *m, uint32_t i, const char *name, char *
 int smaltgpu_sw_full_batch(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
                            const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, int32_t *scores, int packed16);
 
+/* Which sweeps the packed K2a kernel runs in its row-frame form: the largest number of sweep steps (window
+ * rows + G - 1) for these penalties (gap scores negative, as in smaltgpu_params) and a tiling of ncols = G * C read
+ * columns; -1 if the penalties rule the form out.  No device needed. */
+int smaltgpu_sw_rowframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols);
+
 /* The candidate ranking sort of segAliCandsStats (segment.c:1733 -> sort.c:233): `narr` arrays of keys (< 1024), array t
  * in keys[off[t]..off[t+1]); returns the keys and the permutation (index into the array) in the reference's tie order
  * for ranks < nneed (all ranks if nneed < 0; ranks at or beyond nneed may be left unsorted).  in_lds: sort in LDS. */

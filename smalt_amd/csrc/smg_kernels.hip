@@ -394,13 +394,33 @@ __device__ inline us2 pk_max3(us2 a, us2 b, us2 c) {
 __device__ inline uint32_t shr1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, true); }
 
 enum : int { SW16_BLK = 5 };
-struct Sw16Par { uint32_t mm4, dlt, n4; us2 bias, gi, ge; int fp; uint32_t hi_match, hi_mismatch; us2 ngi, nge; };
+struct Sw16Par { uint32_t mm4, dlt, n4; us2 bias, gi, ge; int fp; uint32_t hi_match, hi_mismatch; us2 ngi, nge;
+                 int rf_steps; uint32_t hi_rmatch, hi_rmismatch, hi_rn; us2 pge, ngo; };      // row-frame form (sw16r_core)
 // half-float bit pattern of a small integer (|n| <= 2048: exact)
 __device__ inline uint32_t f16_bits_of_int(int n) {
   if (n == 0) return 0;
   const uint32_t sign = n < 0 ? 0x8000u : 0u, a = (uint32_t)(n < 0 ? -n : n);
   const int e = 31 - __clz((int)a);
   return sign | ((uint32_t)(e + 15) << 10) | ((e <= 10 ? a << (10 - e) : a >> (e - 10)) & 0x3ffu);
+}
+// Row-frame form of the half-float sweep (sw16r_core): the longest sweep (steps = window rows + G - 1) that it may run
+// for these penalties and ncols tile columns, -1 if none.  The shifted scores match + ge, mismatch + ge and ge must be
+// half floats with a zero low byte (v_perm fetches high bytes), and every value must stay an exact integer: the largest
+// is a full-length match seen from the frame of the row after the last, match * ncols + ge * (steps + 1), with gi of room
+// for the sums in between; the smallest, -ge * G - gi in front of the window, is covered by steps >= G - 1.
+__host__ __device__ inline int sw16_rowframe_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
+  const int gi = -gap_init, ge = -gap_ext;
+  if (match <= 0 || ge < 0 || gi < ge || gi > 2040 || mismatch < -1024 || match + ge > 2040) return -1;
+  const int sc[5] = {match + ge, mismatch + ge, ge, match, mismatch};      // the last two: its fallback is sw16f_core, same selectors
+  for (int k = 0; k < 5; k++) {                 // zero low byte: at most three significant bits
+    int a = sc[k] < 0 ? -sc[k] : sc[k];
+    while (a && !(a & 1)) a >>= 1;
+    if (a > 7) return -1;
+  }
+  const int room = 2040 - gi - match * ncols;
+  if (room < 0) return -1;
+  if (ge == 0) return 0x7fffffff;
+  return room / ge - 1;
 }
 // ncols: columns of the register tile (longest read of this instance)
 __device__ inline Sw16Par sw16_par(const MapPar &p, int ncols = 512) {
@@ -415,6 +435,11 @@ __device__ inline Sw16Par sw16_par(const MapPar &p, int ncols = 512) {
   s.hi_match = fm >> 8; s.hi_mismatch = fx >> 8;
   { const uint32_t a = f16_bits_of_int(p.gap_init), e = f16_bits_of_int(p.gap_ext);      // gap_init, gap_ext are negative: added
     s.ngi = us2{(unsigned short)a, (unsigned short)a}; s.nge = us2{(unsigned short)e, (unsigned short)e}; }
+  s.rf_steps = s.fp ? sw16_rowframe_steps(p.match, p.mismatch, p.gap_init, p.gap_ext, ncols) : -1;
+  s.hi_rmatch = f16_bits_of_int(p.match - p.gap_ext) >> 8; s.hi_rmismatch = f16_bits_of_int(p.mismatch - p.gap_ext) >> 8;
+  s.hi_rn = f16_bits_of_int(-p.gap_ext) >> 8;
+  { const uint32_t e = f16_bits_of_int(-p.gap_ext), o = f16_bits_of_int(p.gap_init - p.gap_ext);       // + ge, - (gi - ge)
+    s.pge = us2{(unsigned short)e, (unsigned short)e}; s.ngo = us2{(unsigned short)o, (unsigned short)o}; }
   const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
   s.mm4 = (uint32_t)((p.mismatch + bias) & 0xff) * 0x01010101u;      // a row of mismatches ...
   s.dlt = (uint32_t)(p.match - p.mismatch);                          // ... plus this at the byte of the matching base
@@ -541,6 +566,80 @@ __device__ inline uint32_t sw16f_core(const uint16_t *wrow, int nstep, const uin
   return (uint32_t)(int)(float)best.x | ((uint32_t)(int)(float)best.y << 16);
 }
 
+// The half-float sweep in a row frame: every value of window row r is kept as X + ge * r, so that E, which moves down a
+// column, decays by changing rows and needs no add.  With go = gi - ge, flo_r = ge * r (what a true 0 looks like in row
+// r) and T = H - go:  H(r, j) = max3(H(r-1, j-1) + (s + ge), E, F);  E(r+1, j) = max3(E(r, j), T, flo_(r+1));
+// F(j+1) = max(F(j), T(j)) - ge.  F shares T with E and loses its floor at 0: the floored and the unfloored chain differ
+// only where both are <= 0, and E >= 0 floors H, so H is what it was; F stays >= flo_r - gi.  The + ge of the diagonal is
+// in the score table (sw16_rowtab2r).  Per cell pair: perm, add, max3, add, max3, max, add and 0.6 for the running
+// maximum: 7.6 instructions, one add fewer than sw16f_core.  The running maximum follows the frame (+ ge per row) and
+// comes back to true scores per lane after the loop, because the lanes of a group end on different rows.  Lane g takes
+// H and F of its left neighbour in the same row, hence the same frame; the first lane of a group takes flo_r.  A lane
+// starts on row -g with everything at the true 0 of the row it was last seen from.  sw16_rowframe_steps() says when all
+// of this stays within the exact integers.
+template <int G, int C>
+__device__ inline uint32_t sw16r_core(const uint16_t *wrow, int nstep, const uint32_t (&sel)[C], int g, const Sw16Par &sp, const uint2 *rowtab2r) {
+  hf2 H[C], E[C];
+  const hf2 pge = __builtin_bit_cast(hf2, sp.pge), nge = __builtin_bit_cast(hf2, sp.nge), ngo = __builtin_bit_cast(hf2, sp.ngo);
+  const _Float16 r0 = (_Float16)(-(g + 1));
+  hf2 flo1 = pge * hf2{r0, r0} + pge;          // flo of the row the lane does next: ge * -g
+  {
+    const hf2 f0 = flo1 - pge;
+#pragma unroll
+    for (int cc = 0; cc < C; cc++) { H[cc] = f0; E[cc] = flo1; }
+  }
+  hf2 best = flo1 - pge, F = best, prev_hl = best, flo = best;
+  const uint32_t gmask = g == 0 ? 0u : 0xffffffffu;      // the first lane of a group has no left neighbour: it takes flo
+  for (int step = 0; step < nstep; step++) {
+    const uint2 rr = rowtab2r[wrow[step - g + (G - 1)]];
+    flo = flo1;
+    flo1 = flo + pge;
+    const uint32_t flob = __builtin_bit_cast(uint32_t, flo);
+    // the hand-over runs in every lane (a DPP read of a lane that a branch has switched off yields 0), then a bitwise select
+    const uint32_t hl = (shr1_u32(__builtin_bit_cast(uint32_t, H[C - 1])) & gmask) | (flob & ~gmask);
+    const uint32_t fin = (shr1_u32(__builtin_bit_cast(uint32_t, F)) & gmask) | (flob & ~gmask);
+    hf2 carry = prev_hl;
+    prev_hl = __builtin_bit_cast(hf2, hl);
+    F = __builtin_bit_cast(hf2, fin);
+    // The F chain is four dependent packed operations per cell, and a packed operation that reads the result of the one
+    // before it waits a cycle.  What does not depend on the chain (perm and add of the column two ahead, E, the running
+    // maximum, the row's frame constants) goes between its links, and the order is pinned.
+#define SW16R_SB() __builtin_amdgcn_sched_barrier(0)
+    hf2 t3[C + 2];
+    t3[0] = carry + __builtin_bit_cast(hf2, __builtin_amdgcn_perm(rr.y, rr.x, sel[0]));
+    if (C > 1) t3[1] = H[0] + __builtin_bit_cast(hf2, __builtin_amdgcn_perm(rr.y, rr.x, sel[1]));
+    SW16R_SB();
+#pragma unroll
+    for (int cc = 0; cc < C; cc++) {
+      const hf2 hh = hf_max3(t3[cc], E[cc], F);
+      SW16R_SB();
+      hf2 w = hh;
+      if (cc + 2 < C) w = __builtin_bit_cast(hf2, __builtin_amdgcn_perm(rr.y, rr.x, sel[cc + 2 < C ? cc + 2 : 0]));
+      SW16R_SB();
+      const hf2 tt = hh + ngo;
+      SW16R_SB();
+      if (cc + 2 < C) t3[cc + 2] = H[cc + 1 < C ? cc + 1 : 0] + w;
+      SW16R_SB();
+      const hf2 fm = __builtin_elementwise_maximum(F, tt);
+      SW16R_SB();
+      E[cc] = hf_max3(E[cc], tt, flo1);
+      H[cc] = hh;
+      SW16R_SB();
+      F = fm + nge;
+      SW16R_SB();
+      if (cc & 1) best = hf_max3(best, H[cc - 1], H[cc]);
+      else if (cc == 0) best = best + pge;
+      else if (cc == C - 1) best = __builtin_elementwise_maximum(best, H[cc]);
+      SW16R_SB();
+    }
+#undef SW16R_SB
+  }
+  best = best - flo;                            // true scores, per lane: flo is the frame of the lane's last row
+  for (int o = G / 2; o > 0; o >>= 1)
+    best = __builtin_elementwise_maximum(best, __builtin_bit_cast(hf2, (uint32_t)__shfl_xor((int)__builtin_bit_cast(uint32_t, best), o)));
+  return (uint32_t)(int)(float)best.x | ((uint32_t)(int)(float)best.y << 16);
+}
+
 // rowtab[code]: the four biased ACGT scores against reference code 0..7 (4, 5, 6: 'N' -> score 0; 7 decodes as A upstream)
 __device__ inline void sw16_rowtab(uint32_t *rowtab, const Sw16Par &sp) {
   if (threadIdx.x < 8) rowtab[threadIdx.x] = threadIdx.x < 4 ? sp.mm4 + (sp.dlt << (8 * threadIdx.x)) : sp.n4;
@@ -555,6 +654,15 @@ __device__ inline void sw16_rowtab2(uint2 *rowtab2, const Sw16Par &sp) {
     return;
   }
   rowtab2[threadIdx.x] = make_uint2(a < 4 ? sp.mm4 + (sp.dlt << (8 * a)) : sp.n4, bq < 4 ? sp.mm4 + (sp.dlt << (8 * bq)) : sp.n4);
+}
+// the table of the row-frame form: every score + ge; N rows hold ge (a true 0).  Columns beyond the read keep the selector
+// of the constant 0, now a true score of -ge: such a column influences only columns to its right, and its H never exceeds
+// an H of a real column, so it still cannot raise the maximum.
+__device__ inline void sw16_rowtab2r(uint2 *rowtab2r, const Sw16Par &sp) {
+  const uint32_t a = threadIdx.x & 7u, bq = threadIdx.x >> 3;
+  const uint32_t x4 = sp.hi_rmismatch * 0x01010101u, n4 = sp.hi_rn * 0x01010101u;
+  rowtab2r[threadIdx.x] = make_uint2(a < 4 ? (x4 & ~(0xffu << (8 * a))) | (sp.hi_rmatch << (8 * a)) : n4,
+                                     bq < 4 ? (x4 & ~(0xffu << (8 * bq))) | (sp.hi_rmatch << (8 * bq)) : n4);
 }
 enum : uint32_t { SW16_NPAIR = 5u | (5u << 3) };
 
@@ -685,7 +793,7 @@ __device__ inline void sw16_window(uint16_t *wrow, int g, uint32_t nent, const u
 }
 
 template <int G, int C, int WMAX>
-__global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p, uint32_t ntask_cap) {
+__global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p, uint32_t ntask_cap, int rowframe) {
   // the small-LDS instance (WMAX = SW_SHORT_WMAX) runs first; the large one only sees what is left
   // (through the list S7 made of them; if the list overflowed, by scanning all candidates)
   const unsigned long long nlong = WMAX > SW_SHORT_WMAX ? b.work[WK_LONG_TASKS] : 0;
@@ -693,12 +801,14 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
   const uint32_t *list = (WMAX > SW_SHORT_WMAX && b.long_list && nlong <= b.long_cap) ? b.long_list : nullptr;
   constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
   __shared__ __attribute__((aligned(16))) uint16_t win[NG][sw16_went(G, WMAX)];
-  __shared__ uint2 rowtab2[64];
+  __shared__ uint2 rowtab2[64], rowtab2r[64];
   __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t ntask = list ? (uint32_t)nlong : min(*b.rc_count, ntask_cap), npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
   sw16_rowtab2(rowtab2, sp);
+  const int rf_steps = rowframe ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
+  if (rf_steps >= 0) sw16_rowtab2r(rowtab2r, sp);
   const uint32_t niter = (npair + NG - 1) / NG;                             // iterations of NG task pairs, dealt to the waves in turn
   const bool small = ix.totlen <= 0xffffffffull;
   const int64_t lastw = (int64_t)(ix.totlen / 10);
@@ -764,7 +874,8 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
     uint32_t sel[C];
     sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
-    const uint32_t bb = sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
+    const uint32_t bb = nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)      // nstep is wave-uniform: a scalar branch
+                        : sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
     if ((meta >> 25) & 1u) {                                               // lanes 0 and 1 with a task of their own that was scored
       const int best = (int)((bb >> (16 * g)) & 0xffffu);
       b.rcpool[tix].swscor = best;
@@ -782,16 +893,18 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
 // brings a query of its own, so the selectors take one staging pass per task
 template <int G, int C>
 __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
-                                                       const uint32_t *r_off, uint32_t ntask, MapPar p, int32_t *scores) {
+                                                       const uint32_t *r_off, uint32_t ntask, MapPar p, int32_t *scores, int rowframe) {
   constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
   constexpr int WMAX = SW_FULL_WMAX;
   __shared__ uint16_t win[NG][WMAX + 2 * G];
-  __shared__ uint2 rowtab2[64];
+  __shared__ uint2 rowtab2[64], rowtab2r[64];
   __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
   sw16_rowtab2(rowtab2, sp);
+  const int rf_steps = rowframe ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
+  if (rf_steps >= 0) sw16_rowtab2r(rowtab2r, sp);
   const uint32_t ngroups = gridDim.x * NG;
   for (uint32_t t0 = blockIdx.x * NG; t0 < npair; t0 += ngroups) {
     const uint32_t tp = t0 + grp;
@@ -838,7 +951,8 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
     uint32_t sel[C];
     sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
-    const uint32_t bb = sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
+    const uint32_t bb = nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)      // nstep is wave-uniform: a scalar branch
+                        : sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
     if (g == 0) {
 #pragma unroll
       for (int u = 0; u < 2; u++) {
@@ -1509,12 +1623,23 @@ static bool sw16_ok(const MapPar &p) {
          -p.gap_init >= 0 && -p.gap_init < 30000 && -p.gap_ext >= 0 && -p.gap_ext < 30000;
 }
 
+// test hook: SMALTGPU_SW16_ROWFRAME=0 keeps the packed sweep in its forms without the row frame (sw16f_core, sw16_core), so
+// that both can be compared on the same tasks; read at every launch, which lets one process run both
+static int sw16_rowframe_on() {
+  const char *e = getenv("SMALTGPU_SW16_ROWFRAME");
+  return !(e && e[0] == '0');
+}
+int sw16_rowframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
+  return sw16_rowframe_steps(match, mismatch, gap_init, gap_ext, ncols);
+}
+
 template <int G, int C>
 static void launch_sw_full_t(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t ntask_cap, uint32_t grid) {
   const int use16 = sw16_ok(p);
   if (use16) {
-    hipLaunchKernelGGL((k_sw_full16<G, C, SW_SHORT_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap);
-    hipLaunchKernelGGL((k_sw_full16<G, C, SW_FULL_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap);
+    const int rf = sw16_rowframe_on();
+    hipLaunchKernelGGL((k_sw_full16<G, C, SW_SHORT_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
+    hipLaunchKernelGGL((k_sw_full16<G, C, SW_FULL_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
   }
   hipLaunchKernelGGL((k_sw_full<G, C>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, use16);
 }
@@ -1566,7 +1691,7 @@ int launch_sw_scalar(hipStream_t s, const Batch &b, const DevIndex &ix, const Ma
 template <int G, int C>
 static void launch_sw_raw_t(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n,
                             const MapPar &p, int32_t *sc, uint32_t grid, int packed16) {
-  if (packed16) hipLaunchKernelGGL((k_sw_full16_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc);
+  if (packed16) hipLaunchKernelGGL((k_sw_full16_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc, sw16_rowframe_on());
   else hipLaunchKernelGGL((k_sw_full_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc);
 }
 
