@@ -410,7 +410,11 @@ enum { SMALTGPU_FMT_CIGAR = 0, SMALTGPU_FMT_SAM = 1, SMALTGPU_FMT_SSAHA = 2 };  
                                                                                           * report.c:579).  -f gff ends the reference program with a memory
                                                                                           * fault on its first read (report.c:1389-1401 drops the block list
                                                                                           * it has just made), -f bam needs a library this build has not */
-enum { SMALTGPU_REP_SOFTCLIP = 0x02, SMALTGPU_REP_HEADER = 0x04, SMALTGPU_REP_XMISMATCH = 0x08 };   /* REPORTMODIF_* (report.h:54-59) */
+enum { SMALTGPU_REP_ALIOUT = 0x01, SMALTGPU_REP_SOFTCLIP = 0x02, SMALTGPU_REP_HEADER = 0x04, SMALTGPU_REP_XMISMATCH = 0x08 };   /* REPORTMODIF_* (report.h:54-59);
+                                                                                          * ALIOUT (smalt map -a): the line of every mapped alignment, of any
+                                                                                          * format, is followed by the alignment itself in blocks of three rows
+                                                                                          * -- read, markers, reference -- 60 columns wide; needs
+                                                                                          * smaltgpu_report_set_reference */
 enum { SMALTGPU_OUT_BEST = 0x01, SMALTGPU_OUT_SINGLE = 0x02, SMALTGPU_OUT_SPLIT = 0x04, SMALTGPU_OUT_RANDSEL = 0x08 };   /* RESULTFLG_* (results.h:55-63); SPLIT: the best
                                                                                           * alignments of the other read segments follow as partial ones (results.c:2250-2278, :2337) */
 typedef struct smaltgpu_report_opts {
@@ -471,6 +475,16 @@ int smaltgpu_inshist_count(const smaltgpu_inshist *h, int32_t insert_size, int s
  * insert_min / insert_max of the smaltgpu_pair_opts it hands to smaltgpu_map_pairs AND smaltgpu_report_emit_pairs to the
  * histogram's bounds (updateInsertBoundariesFromSample, smalt.c:417-426) */
 int smaltgpu_report_set_inshist(smaltgpu_report *rp, const smaltgpu_inshist *h);
+/* the host copy of the packed reference (smaltgpu_index_packed_host) for the alignment blocks of SMALTGPU_REP_ALIOUT (fprintAlignment,
+ * report.c:248-388, called from writeReportForRead, report.c:1521-1526): the reference row of a block is read from it at the sequence
+ * offsets smaltgpu_report_header was given.  Borrowed: it must outlive the report; NULL detaches it.  The emit functions return
+ * SMALTGPU_EARG when the flag is set and no reference, or no header call, came first -- they never print lines without their blocks.
+ * A block is "    QUERY: <first> <letters> <last>", a row of markers under the letters (blank: match, i: transition, v: transversion,
+ * ?: a letter other than ACGT takes part, -: gap) and "REFERENCE: <first> <letters> <last>", then two empty lines.  Coordinates are
+ * 1-based, the reference's within its sequence; the read of a reverse alignment is shown as its reverse complement with descending
+ * coordinates.  A line breaks after 60 columns, gaps included; an alignment of exactly 60, 120, ... columns ends with one more block of
+ * empty rows, as in the reference program. */
+int smaltgpu_report_set_reference(smaltgpu_report *rp, const uint32_t *packed_host);
 /* per pair of the last smaltgpu_report_emit_pairs call on this report: the insert size `smalt sample` would add to its sample and
  * whether there is one (resultSetInferInsertSize, results.c:2460-2483, called behind the report of the pair: smalt.c:1180-1182).
  * The arrays belong to the report and hold until its next emit call */

@@ -90,7 +90,7 @@ class ReportOpts(C.Structure):         # smaltgpu_report_opts
 
 
 FMT_CIGAR, FMT_SAM, FMT_SSAHA = 0, 1, 2
-REP_SOFTCLIP, REP_HEADER, REP_XMISMATCH = 0x02, 0x04, 0x08
+REP_ALIOUT, REP_SOFTCLIP, REP_HEADER, REP_XMISMATCH = 0x01, 0x02, 0x04, 0x08
 OUT_BEST, OUT_SINGLE, OUT_SPLIT, OUT_RANDSEL = 0x01, 0x02, 0x04, 0x08
 
 
@@ -203,6 +203,9 @@ def lib():
         L.smaltgpu_inshist_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
         L.smaltgpu_inshist_count.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.smaltgpu_report_set_inshist.argtypes = [C.c_void_p, C.c_void_p]
+        L.smaltgpu_index_packed_host.restype = C.c_void_p
+        L.smaltgpu_index_packed_host.argtypes = [C.c_void_p]
+        L.smaltgpu_report_set_reference.argtypes = [C.c_void_p, C.c_void_p]      # the packed host copy (smaltgpu_index_packed_host) for REP_ALIOUT
         L.smaltgpu_report_pair_inserts.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32)]
         _lib = L
     return _lib

@@ -1,7 +1,8 @@
 // smaltgpu-map -- `smalt map` for single reads and read pairs on top of the C ABI of include/smaltgpu.h, file to file:
 //   FASTQ/FASTA text --smaltgpu_reads_parse--> batch --smaltgpu_map_batch (GPU)--> raw alignments
 //   --smaltgpu_postprocess--> mapping qualities, order --smaltgpu_report_emit--> CIGAR / SAM text;
-//   two files of mates: --smaltgpu_map_pairs (the rounds of rmapPair on the GPU)--> --smaltgpu_report_emit_pairs--> text.
+//   two files of mates: --smaltgpu_map_pairs (the rounds of rmapPair on the GPU)--> --smaltgpu_report_emit_pairs--> text;
+//   -a: the report also gets the host copy of the packed reference and prints every mapped alignment in blocks behind its line.
 // The option letters, defaults and derived flags follow the reference's `smalt map` (menu.c:1147-1160 defaults,
 // :1340-1345 -d, :1487-1497 -r; smalt.c:209-245 output formats, :490-503 result flags, :608-615 default -m) so that the
 // same command line prints the same lines (tests/test_gpu_report.py).  Host code only: it needs libsmaltgpu.so, not hipcc.
@@ -58,6 +59,9 @@ void usage() {
           "  -x         more sensitive search (all seeds, deeper candidate lists)\n"
           "  -p         split reads: a second alignment for the part of a read (or mate) its best alignment leaves uncovered\n"
           "  -w         complexity-weighted alignment scores: an alignment over a low-complexity stretch of the reference scores less\n"
+          "  -a         explicit alignments: the line of every mapped alignment is followed by the read and the reference side by side in\n"
+          "             blocks of 60 columns, with a row of markers between them (i transition, v transversion, ? other letter, - gap)\n"
+          "  -O         accepted without effect: the output is in the order of the input anyway\n"
           "  -q <int>   base quality threshold for k-mer words\n"
           "  -S <spec>  alignment scores, e.g. match=1,subst=-2,gapopen=-4,gapext=-3 (the default; any subset)\n"
           "  -n <int>   host threads for parsing, post-processing and formatting (default: up to 16)\n"
@@ -68,8 +72,7 @@ void usage() {
           "  -l <lib>   pair library: pe (default) | mp | pp\n"
           "  -I <file>  histogram of insert sizes written by `sample` (the reference's `smalt map -g <file>`; -g names the devices here):\n"
           "             it widens the insert range and weighs the pairings of a pair; its two prints go to standard output\n"
-          "with two read files the reads are mapped as pairs (read i of the first with read i of the second file);\n"
-          "-a goes through the bound reference program (INTEGRATION.md)\n"
+          "with two read files the reads are mapped as pairs (read i of the first with read i of the second file)\n"
           "\n"
           "usage: smaltgpu-map sample [-m <int>] [-n <int>] [-o <file>] [-q <int>] [-u <int>] [-B <int>] [-g <list>] <index prefix> <reads> <mates>\n"
           "  `smalt sample`: maps every <u>-th pair (default 100; every (pairs / 4098)-th when that is fewer) and writes the SAM lines\n"
@@ -229,7 +232,7 @@ int main(int argc, char **argv) {
   const char *fmt = sampling ? "sam:nohead" : "cigar", *oufil = nullptr, *scorespec = nullptr, *histfil = nullptr;   // sample prints SAM lines without a header
   int m = -1, d = 0, seed = 0, q = 0, nthreads = 0, ins_max = 500, ins_min = 0, lib = SMALTGPU_LIB_PE, every = 100;    // -u: MENU_DEFAULTS_READSKIP (menu.c:618)
   std::vector<int> devices;
-  bool d_given = false, randrepeat = true, exhaustive = false, split = false, weighted = false;
+  bool d_given = false, randrepeat = true, exhaustive = false, split = false, weighted = false, aliout = false;
   double minid = 0.0, mincover = 0.0;
   long batch = 262144;
   int a = sampling ? 2 : 1;
@@ -238,9 +241,11 @@ int main(int argc, char **argv) {
     if (o == 'x' && !argv[a][2]) { exhaustive = true; continue; }
     if (o == 'p' && !argv[a][2]) { split = true; continue; }
     if (o == 'w' && !argv[a][2] && !sampling) { weighted = true; continue; }       // (the reference's `sample` has no -w)
+    if (o == 'a' && !argv[a][2] && !sampling) { aliout = true; continue; }         // (nor -a)
+    if (o == 'O' && !argv[a][2] && !sampling) continue;                            // output in input order: always the case here
     if (sampling && !strchr("mnoquBg", o)) usage();
     if (argv[a][2] || !strchr("fomdrycqnBgijlSIu", o) || (o == 'u' && !sampling)) {
-      if (strchr("TFa", o) && !argv[a][2]) die("option not supported by this program (use the bound `smalt map`, INTEGRATION.md)", argv[a]);
+      if (strchr("TF", o) && !argv[a][2]) die("option not supported by this program (use the bound `smalt map`, INTEGRATION.md)", argv[a]);
       usage();
     }
     if (a + 1 >= argc) usage();
@@ -306,6 +311,7 @@ int main(int argc, char **argv) {
       p = e;
     }
   }
+  if (aliout) ro.modflags |= SMALTGPU_REP_ALIOUT;                                        // REPORTMODIF_ALIOUT (smalt.c:492-493)
   ro.min_swscor = m >= 0 ? m : 18;                                                       // resultSetFilterData gets the menu's value (smalt.c:490, menu.c:599)
   ro.min_swscor_below_max = d;
   ro.min_identity = minid;
@@ -405,6 +411,11 @@ int main(int argc, char **argv) {
 
   smaltgpu_report *rep = smaltgpu_report_create();
   if (hist && smaltgpu_report_set_inshist(rep, hist)) die("-I", smaltgpu_last_error());
+  if (aliout) {                                                                          // the blocks show the reference, also where post-processing does not need it
+    const uint32_t *shown = packed ? packed : smaltgpu_index_packed_host(ix);
+    if (!shown) die("index", smaltgpu_last_error());
+    if (smaltgpu_report_set_reference(rep, shown)) die("-a", smaltgpu_last_error());
+  }
   {
     const char *htxt; uint64_t hlen;
     if (smaltgpu_report_header(rep, seqnames, sop, nseq, &ro, "smaltgpu-map", VERSION, argc, (const char *const *)argv, &htxt, &hlen)) die("header", smaltgpu_last_error());

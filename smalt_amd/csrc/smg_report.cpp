@@ -379,6 +379,8 @@ struct ReadCtx {
   const char *const *seqnames;
   int64_t nseq;
   const uint32_t *seqlen;                // lengths of the reference sequences (SSAHA lines print them): from smaltgpu_report_header
+  const uint64_t *seqoff = nullptr;      // their offsets in the concatenated reference and its packed host copy (smaltgpu_report_set_reference):
+  const uint32_t *packed = nullptr;      // for the alignment blocks of SMALTGPU_REP_ALIOUT
 };
 
 // the alignments of read i in the order the reference's report holds them; draw: the pre-drawn index for a random choice
@@ -635,11 +637,114 @@ bool print_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a, con
   }
 }
 
+// ---- explicit alignment blocks (smalt map -a: what fprintAlignment prints behind the line of a mapped alignment, report.c:248-388) ----
+// The alignment string is expanded once into three rows of equal length -- read, markers, reference, one character per alignment
+// column -- and the rows are then cut into blocks of ALI_WIDTH columns.  A block names the first and the last letter of each row
+// that it holds; gap columns take room in the line but no letter.  The reference decides whether another block follows when a line
+// is full, before it has seen that the string ends: an alignment of exactly 60, 120, ... columns is followed by one block
+// with empty rows, whose start coordinates lie one letter behind its end coordinates.
+enum { ALI_WIDTH = 60 };                                   // DEFAULT_LINWIDTH_ALI (report.c:50); no option sets another
+enum : char { ALI_SAME = ' ', ALI_GAP = '-', ALI_TRANSITION = 'i', ALI_TRANSVERSION = 'v', ALI_UNKNOWN = '?', ALI_NONSTANDARD = '!' };   // report.c:100-105
+
+struct AliRows { std::string read, mark, ref; };           // scratch of one formatting thread
+
+// marker of a substitution column from the classes of its two letters (seqCodecFindBaseClass, sequence.c:441-452): A and G are purines,
+// C and T pyrimidines, every other letter counts as unknown, the end of a string as non-standard
+char substitution_mark(char q, char s) {
+  auto letter_class = [](char c) { return (c == 'A' || c == 'G') ? 0 : (c == 'C' || c == 'T') ? 1 : c ? 2 : 3; };
+  const int cq = letter_class(q), cs = letter_class(s);
+  if (cq == 3 || cs == 3) return ALI_NONSTANDARD;
+  if (cq == 2 || cs == 2) return ALI_UNKNOWN;
+  return cq == cs ? ALI_TRANSITION : ALI_TRANSVERSION;
+}
+
+// the three rows of alignment a of read i -> false when the string and the two ranges do not fit together
+bool expand_alignment(AliRows &w, const ReadCtx &cx, uint32_t i, const Ali &a) {
+  static const char REF_LETTER[] = "ACGTXNN";              // 3-bit codes as uncompressSeq spells them (sequence.c:1499-1550); 7 ends the reference
+  const uint64_t r0 = cx.rv->read_off[i];
+  const uint32_t qlen = (uint32_t)(cx.rv->read_off[i + 1] - r0);
+  if (!a.dstr || a.qs < 1 || a.qs > a.qe || a.qe > qlen || a.sidx < 0 || a.sidx >= cx.nseq || a.ss < 1 || a.ss > a.se || a.se > cx.seqlen[a.sidx]) return false;
+  const uint8_t *seq = cx.rv->bases + r0;
+  const bool rev = (a.status & MF_REVERSE) != 0;
+  const uint32_t nq = a.qe - a.qs + 1;
+  const uint64_t ns = a.se - a.ss + 1, ref0 = cx.seqoff[a.sidx] + a.ss - 1;
+  uint32_t qi = 0;
+  uint64_t si = 0;
+  bool fits = true;
+  // the next letter of the read in the direction of the alignment (reversed: the complement, letters other than ACGT stay) and of the reference
+  auto read_letter = [&]() -> char {
+    if (qi >= nq) { fits = false; return ALI_UNKNOWN; }
+    const uint8_t c = rev ? seq[a.qe - 1 - qi] : seq[a.qs - 1 + qi];
+    qi++;
+    return (char)(!rev ? c : c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c);
+  };
+  auto ref_letter = [&]() -> char {
+    if (si >= ns) { fits = false; return ALI_UNKNOWN; }
+    const uint64_t at = ref0 + si++;
+    const unsigned code = (cx.packed[at / 10] >> (3 * (9 - (unsigned)(at % 10)))) & 7u;
+    if (code == 7) { fits = false; return ALI_UNKNOWN; }
+    return REF_LETTER[code];
+  };
+  auto column = [&](char q, char m, char s) { w.read.push_back(q); w.mark.push_back(m); w.ref.push_back(s); };
+  w.read.clear(); w.mark.clear(); w.ref.clear();
+  bool closed = false;
+  for (const uint8_t *d = a.dstr; *d && fits; d++) {
+    unsigned run, op;
+    dget(*d, &run, &op);
+    for (unsigned k = 0; k < run; k++) column(read_letter(), ALI_SAME, ref_letter());      // the matches in front of the operation
+    if (op == 0) column(read_letter(), ALI_SAME, ref_letter());                              // M: one more match (a run of 62 in one code)
+    else if (op == 1) column(ALI_GAP, ALI_GAP, ref_letter());                                // D: the read lacks a base
+    else if (op == 2) column(read_letter(), ALI_GAP, ALI_GAP);                               // I: the read has a base more
+    else if (d[1]) { const char q = read_letter(), s = ref_letter(); column(q, substitution_mark(q, s), s); }
+    else closed = true;                                                                      // the S that ends the string stands for no column
+  }
+  return fits && closed;
+}
+
+bool put_alignment_blocks(std::string &o, AliRows &w, const ReadCtx &cx, uint32_t i, const Ali &a) {
+  if (!expand_alignment(w, cx, i, a)) return false;
+  const bool rev = (a.status & MF_REVERSE) != 0;
+  const size_t ncol = w.mark.size();
+  char buf[64];
+  uint32_t q_done = 0;
+  uint64_t s_done = 0;
+  for (size_t c0 = 0;; c0 += ALI_WIDTH) {
+    const size_t n = ncol - c0 < (size_t)ALI_WIDTH ? ncol - c0 : (size_t)ALI_WIDTH;
+    uint32_t q_here = 0, s_here = 0;
+    for (size_t c = c0; c < c0 + n; c++) {
+      const bool gap = w.mark[c] == ALI_GAP;
+      if (!gap || w.read[c] != ALI_GAP) q_here++;
+      if (!gap || w.ref[c] != ALI_GAP) s_here++;
+    }
+    const int q_first = rev ? (int)(a.qe - q_done) : (int)(a.qs + q_done), q_last = rev ? (int)(a.qe - (q_done + q_here) + 1) : (int)(a.qs + q_done + q_here - 1);
+    snprintf(buf, sizeof(buf), "    QUERY: %10i ", q_first);
+    o += buf; o.append(w.read, c0, n);
+    snprintf(buf, sizeof(buf), " %-10i\n                      ", q_last);
+    o += buf; o.append(w.mark, c0, n);
+    snprintf(buf, sizeof(buf), "\nREFERENCE: %10i ", (int)(a.ss + s_done));
+    o += buf; o.append(w.ref, c0, n);
+    snprintf(buf, sizeof(buf), " %-10i\n\n\n", (int)(a.ss + s_done + s_here - 1));
+    o += buf;
+    q_done += q_here; s_done += s_here;
+    if (n < (size_t)ALI_WIDTH) break;                       // a full line: the reference goes round once more
+  }
+  return true;
+}
+
+// the line of an alignment and, with SMALTGPU_REP_ALIOUT, the blocks of a mapped one behind it (writeReportForRead, report.c:1486-1534)
+bool print_entry(std::string &o, AliRows &w, const ReadCtx &cx, uint32_t i, const Ali &a, const PairSide *ps) {
+  if (!print_line(o, cx, i, a, ps)) return false;
+  if (!(cx.op->modflags & SMALTGPU_REP_ALIOUT) || !(a.status & MF_MAPPED)) return true;
+  return put_alignment_blocks(o, w, cx, i, a);
+}
+
 }  // namespace
 
 struct smaltgpu_report {
   std::string text; std::vector<std::string> part; std::vector<int> draw; std::vector<uint32_t> seqlen;
   const smaltgpu_inshist *hist = nullptr;                          // smaltgpu_report_set_inshist
+  std::vector<uint64_t> seqoff;                                    // smaltgpu_report_header: offsets of the sequences in the concatenated reference
+  const uint32_t *packed = nullptr;                                // smaltgpu_report_set_reference (borrowed)
   std::vector<int32_t> insert_size; std::vector<uint8_t> insert_known;      // per pair of the last smaltgpu_report_emit_pairs
   uint32_t npairs_emitted = 0;
 };
@@ -649,6 +754,8 @@ int check_format(const smaltgpu_report *rp, const smaltgpu_report_opts *op, int6
   if (op->format != SMALTGPU_FMT_CIGAR && op->format != SMALTGPU_FMT_SAM && op->format != SMALTGPU_FMT_SSAHA) return smaltgpu_set_error(SMALTGPU_EARG, "unknown output format");
   if (op->format == SMALTGPU_FMT_SSAHA && (int64_t)rp->seqlen.size() != nseq)
     return smaltgpu_set_error(SMALTGPU_EARG, "SSAHA lines carry the sequence lengths: call smaltgpu_report_header on this report first");
+  if ((op->modflags & SMALTGPU_REP_ALIOUT) && (!rp->packed || (int64_t)rp->seqoff.size() != nseq + 1))
+    return smaltgpu_set_error(SMALTGPU_EARG, "alignment blocks (SMALTGPU_REP_ALIOUT) show the reference: call smaltgpu_report_header and smaltgpu_report_set_reference on this report first");
   return SMALTGPU_OK;
 }
 }  // namespace
@@ -663,6 +770,7 @@ extern "C" int smaltgpu_report_header(smaltgpu_report *rp, const char *const *se
   o.clear();
   rp->seqlen.resize((size_t)nseq);
   for (int64_t s = 0; s < nseq; s++) rp->seqlen[(size_t)s] = (uint32_t)(sop[s + 1] - sop[s]);
+  rp->seqoff.assign(sop, sop + nseq + 1);
   if (op->format == SMALTGPU_FMT_SAM && (op->modflags & SMALTGPU_REP_HEADER)) {       // writeSAMHeaderf (report.c:1266-1300)
     char buf[64];
     o += "@HD\tVN:1.3\tSO:unknown\n";
@@ -686,7 +794,7 @@ extern "C" int smaltgpu_report_emit(smaltgpu_report *rp, const smaltgpu_post_out
   if (post->nreads != reads->nreads) return smaltgpu_set_error(SMALTGPU_EARG, "results and reads differ in number");
   if (int e = check_format(rp, op, nseq)) return e;
   const uint32_t n = post->nreads;
-  ReadCtx cx{post, reads, op, seqnames, nseq, rp->seqlen.data()};
+  ReadCtx cx{post, reads, op, seqnames, nseq, rp->seqlen.data(), rp->seqoff.data(), rp->packed};
   for (uint32_t i = 0; i < n; i++) {
     if (post->needs_reference[i]) return smaltgpu_set_error(SMALTGPU_EARG, "a read was left to the caller by smaltgpu_postprocess (needs_reference): give it the packed reference");
     if (raw && raw->stat[i].errcode) {               // the reference stops at a read that fails (rmap.c:1417 -> smalt.c: the message names the read)
@@ -712,12 +820,13 @@ extern "C" int smaltgpu_report_emit(smaltgpu_report *rp, const smaltgpu_post_out
     o.clear();
     std::vector<Ali> alis;
     std::vector<uint32_t> st;
+    AliRows rows;
     const uint32_t lo = (uint32_t)((uint64_t)n * (uint64_t)t / (uint64_t)nthreads), hi = (uint32_t)((uint64_t)n * (uint64_t)(t + 1) / (uint64_t)nthreads);
-    o.reserve((size_t)(hi - lo) * (op->format == SMALTGPU_FMT_SAM ? 420 : 96));
+    o.reserve((size_t)(hi - lo) * ((op->format == SMALTGPU_FMT_SAM ? 420 : 96) + ((op->modflags & SMALTGPU_REP_ALIOUT) ? 640 : 0)));
     for (uint32_t i = lo; i < hi; i++) {
       if (!select_read(cx, i, rp->draw[i], alis, st)) { bad[(size_t)t] = (int)i; return; }
       for (const Ali &a : alis) {
-        const bool ok = print_line(o, cx, i, a, nullptr);
+        const bool ok = print_entry(o, rows, cx, i, a, nullptr);
         if (!ok) { bad[(size_t)t] = (int)i; return; }
       }
     }
@@ -858,11 +967,11 @@ bool sampled_insert(const Table &A, const Table &B, int32_t *size) {
   return true;
 }
 
-bool pair_lines(std::string &o, const PairJob &jb, uint32_t p, const Table &A, const Table &B, const std::vector<Entry> &entries, PairSheet &sh) {
+bool pair_lines(std::string &o, const PairJob &jb, uint32_t p, const Table &A, const Table &B, const std::vector<Entry> &entries, PairSheet &sh, AliRows &rows) {
   sh.clear();
   for (const Entry &e : entries) sheet_add(sh, e, A, B);
   if ((jb.op->outflags & SMALTGPU_OUT_BEST) && (jb.op->outflags & SMALTGPU_OUT_SPLIT)) { sheet_add_partial(sh, 0, A); sheet_add_partial(sh, 1, B); }
-  auto line = [&](int w, const Ali &a, const PairSide *ps) { return print_line(o, jb.cx[w], p, a, ps); };
+  auto line = [&](int w, const Ali &a, const PairSide *ps) { return print_entry(o, rows, jb.cx[w], p, a, ps); };
   for (int w = 0; w < 2; w++) sh.printed[w].assign(sh.side[w].size(), 0);
   for (const PairSheet::Link &ln : sh.links) {                       // reportWrite (report.c:1758-1867): the pairs first ...
     const Ali &a = sh.side[0][(size_t)ln.ia], &b = sh.side[1][(size_t)ln.ib];
@@ -885,7 +994,8 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
   const uint32_t n = pairs->blk.npairs;
   if (reads->nreads != n || mates->nreads != n) return smaltgpu_set_error(SMALTGPU_EARG, "smaltgpu_report_emit_pairs: reads, mates and mapped pairs differ in number");
   if (int e = check_format(rp, op, nseq)) return e;
-  PairJob jb{pairs, {ReadCtx{nullptr, reads, op, seqnames, nseq, rp->seqlen.data()}, ReadCtx{nullptr, mates, op, seqnames, nseq, rp->seqlen.data()}}, op, po,
+  PairJob jb{pairs, {ReadCtx{nullptr, reads, op, seqnames, nseq, rp->seqlen.data(), rp->seqoff.data(), rp->packed},
+                     ReadCtx{nullptr, mates, op, seqnames, nseq, rp->seqlen.data(), rp->seqoff.data(), rp->packed}}, op, po,
              rp->hist ? &rp->hist->h : nullptr};
   rp->insert_size.assign(n ? n : 1, 0);
   rp->insert_known.assign(n ? n : 1, 0);
@@ -905,6 +1015,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
     smgpairs::Join join;
     std::vector<Entry> entries;
     PairSheet sh;
+    AliRows rows;
     for (uint32_t j = lo; j < hi; j++) {
       const uint32_t p = second ? (*todo)[j] : j;
       smgpairs::Draws dr;
@@ -912,7 +1023,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
       if (!pair_entries(jb, p, A, B, join, entries, dr)) { if (bad[(size_t)t] < 0) bad[(size_t)t] = p; continue; }
       if (!second && drawing && dr.used > 0) { need[p] = (uint8_t)dr.used; continue; }
       const uint64_t at = o.size();
-      if (!pair_lines(o, jb, p, A, B, entries, sh)) { if (bad[(size_t)t] < 0) bad[(size_t)t] = p; continue; }
+      if (!pair_lines(o, jb, p, A, B, entries, sh, rows)) { if (bad[(size_t)t] < 0) bad[(size_t)t] = p; continue; }
       where[p] = Slice{(uint32_t)t, at, o.size() - at};
       rp->insert_known[p] = sampled_insert(A, B, &rp->insert_size[p]) ? 1 : 0;
     }
@@ -921,7 +1032,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; t++) {
       const uint32_t lo = (uint32_t)((uint64_t)n * t / nthreads), hi = (uint32_t)((uint64_t)n * (t + 1) / nthreads);
-      rp->part[(size_t)t].reserve((size_t)(hi - lo) * (op->format == SMALTGPU_FMT_SAM ? 840 : 192));
+      rp->part[(size_t)t].reserve((size_t)(hi - lo) * ((op->format == SMALTGPU_FMT_SAM ? 840 : 192) + ((op->modflags & SMALTGPU_REP_ALIOUT) ? 1280 : 0)));
       if (nthreads == 1) pass(0, lo, hi, false, nullptr, nullptr, nullptr); else th.emplace_back(pass, t, lo, hi, false, nullptr, nullptr, nullptr);
     }
     for (std::thread &x : th) x.join();
@@ -957,6 +1068,12 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
 extern "C" int smaltgpu_report_set_inshist(smaltgpu_report *rp, const smaltgpu_inshist *h) {
   if (!rp) return smaltgpu_set_error(SMALTGPU_EARG, "smaltgpu_report_set_inshist: null argument");
   rp->hist = h;
+  return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_report_set_reference(smaltgpu_report *rp, const uint32_t *packed_host) {
+  if (!rp) return smaltgpu_set_error(SMALTGPU_EARG, "smaltgpu_report_set_reference: null argument");
+  rp->packed = packed_host;
   return SMALTGPU_OK;
 }
 

@@ -3,7 +3,8 @@
 alone) on the same two read files -- reference shape, read length, insert distribution, library type, output format and
 search options drawn per case.  Prints one line per case and the first differing lines; exit status 1 if any case differs.
 usage: fuzz_pairs.py [ncases] [npairs] [seed]        (GPU box; needs make -C oracle ref)
-FUZZ_BOUND=1 compares the bound program (oracle/_ref/smalt_gpu) instead of smaltgpu-map."""
+FUZZ_BOUND=1 compares the bound program (oracle/_ref/smalt_gpu) instead of smaltgpu-map.
+FUZZ_ALI=1: both programs print the explicit alignment blocks too (-a); the cases of a seed stay the same."""
 import os
 import subprocess
 import sys
@@ -90,6 +91,8 @@ def main():
                 open(os.path.join(tmp, "case.txt"), "w").write("%d %d %s\n%s\n" % (k, s, " ".join(fqs), " ".join(opts)))
                 print("case %d kept in %s: %s" % (case, tmp, " ".join(opts)))
                 return 0
+            if os.environ.get("FUZZ_ALI"):            # behind every draw of an option: the random stream of a seed is the one without it
+                opts = opts + ["-a"]
             ref_out, gpu_out = os.path.join(tmp, "ref.out"), os.path.join(tmp, "gpu.out")
             r0 = subprocess.run([t.SMALT, "map"] + opts + ["-o", ref_out, pre] + fqs, capture_output=True)
             if r0.returncode:

@@ -4,7 +4,8 @@ alone) on the same read file -- reference shape, index word length and stride, r
 drawn per case.  Prints one line per case and the first differing lines; exit status 1 if any case differs.
 usage: fuzz_single.py [ncases] [nreads] [seed]        (GPU box; needs make -C oracle ref)
 FUZZ_BOUND=1 compares the bound program (oracle/_ref/smalt_gpu) instead of smaltgpu-map.
-FUZZ_SPLIT=1: split reads (-p) on chimeric reads (tests/test_gpu_split.py), SSAHA lines and user scores (-S) among the draws."""
+FUZZ_SPLIT=1: split reads (-p) on chimeric reads (tests/test_gpu_split.py), SSAHA lines and user scores (-S) among the draws.
+FUZZ_ALI=1: both programs print the explicit alignment blocks too (-a); the cases of a seed stay the same."""
 import os
 import subprocess
 import sys
@@ -76,6 +77,8 @@ def main():
             if r0.returncode:
                 print("case %d: the reference rejects the index k=%d s=%d" % (case, k, s), flush=True)
                 continue
+            if os.environ.get("FUZZ_ALI"):            # behind every draw of an option: the random stream of a seed is the one without it
+                opts = opts + ["-a"]
             ref_out, gpu_out = os.path.join(tmp, "ref.out"), os.path.join(tmp, "gpu.out")
             r0 = subprocess.run([t.SMALT, "map"] + opts + ["-o", ref_out, pre, fq], capture_output=True)
             if r0.returncode:
