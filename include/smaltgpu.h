@@ -515,6 +515,8 @@ int smaltgpu_sw_full_batch(smaltgpu_mapper *m, const uint8_t *qcodes, const uint
  * rows + G - 1) for these penalties (gap scores negative, as in smaltgpu_params) and a tiling of ncols = G * C read
  * columns; -1 if the penalties rule the form out.  No device needed. */
 int smaltgpu_sw_rowframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols);
+/* The same for the pair-frame form, which the kernel tries first: every sweep of at most this many steps runs in it. */
+int smaltgpu_sw_pairframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols);
 
 /* The candidate ranking sort of segAliCandsStats (segment.c:1733 -> sort.c:233): `narr` arrays of keys (< 1024), array t
  * in keys[off[t]..off[t+1]); returns the keys and the permutation (index into the array) in the reference's tie order

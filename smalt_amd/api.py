@@ -194,6 +194,7 @@ def lib():
         L.smaltgpu_sw_full_batch.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p,
                                              C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Params), C.POINTER(C.c_int32), C.c_int]
         L.smaltgpu_sw_rowframe_max_steps.argtypes = [C.c_int] * 5
+        L.smaltgpu_sw_pairframe_max_steps.argtypes = [C.c_int] * 5
         L.smaltgpu_rank_sort_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.smaltgpu_sample_interval.argtypes = [C.c_uint64, C.c_int]
         L.smaltgpu_inshist_from_sample.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_uint64]

@@ -1320,6 +1320,10 @@ extern "C" int smaltgpu_sw_rowframe_max_steps(int match, int mismatch, int gap_i
   return sw16_rowframe_max_steps(match, mismatch, gap_init, gap_ext, ncols);
 }
 
+extern "C" int smaltgpu_sw_pairframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
+  return sw16_pairframe_max_steps(match, mismatch, gap_init, gap_ext, ncols);
+}
+
 extern "C" int smaltgpu_rank_sort_batch(smaltgpu_mapper *m, const uint32_t *keys, const uint32_t *off, uint32_t narr, int nneed, int in_lds,
                                          uint32_t *out_keys, uint32_t *out_idx) {
   if (!m || !keys || !off || !out_keys || !out_idx) return fail(SMALTGPU_EARG, "null argument");

@@ -46,6 +46,8 @@ int launch_sw_full_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, cons
 // longest sweep (window rows + G - 1) that the packed K2a kernel runs in its row-frame form for these penalties and this
 // many tile columns (G * C); -1: none
 int sw16_rowframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols);
+// the same for its pair-frame form, which goes first
+int sw16_pairframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols);
 int launch_rank_sort_raw(hipStream_t s, const uint32_t *keys, const uint32_t *off, uint32_t narr, int nneed, int in_lds, uint32_t *kv,
                          uint32_t *out_key, uint32_t *out_idx);
 

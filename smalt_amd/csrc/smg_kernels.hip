@@ -395,7 +395,8 @@ __device__ inline uint32_t shr1_u32(uint32_t v) { return (uint32_t)__builtin_amd
 
 enum : int { SW16_BLK = 5 };
 struct Sw16Par { uint32_t mm4, dlt, n4; us2 bias, gi, ge; int fp; uint32_t hi_match, hi_mismatch; us2 ngi, nge;
-                 int rf_steps; uint32_t hi_rmatch, hi_rmismatch, hi_rn; us2 pge, ngo; };      // row-frame form (sw16r_core)
+                 int rf_steps; uint32_t hi_rmatch, hi_rmismatch, hi_rn; us2 pge, ngo;         // row-frame form (sw16r_core)
+                 int pf_steps; uint32_t hi_pmatch, hi_pmismatch, hi_pn; us2 nge2; };          // pair-frame form (sw16p_core)
 // half-float bit pattern of a small integer (|n| <= 2048: exact)
 __device__ inline uint32_t f16_bits_of_int(int n) {
   if (n == 0) return 0;
@@ -422,6 +423,24 @@ __host__ __device__ inline int sw16_rowframe_steps(int match, int mismatch, int 
   if (ge == 0) return 0x7fffffff;
   return room / ge - 1;
 }
+// Pair-frame form (sw16p_core): the same question.  Its tables are the row frame's, the plain one and one of scores + 2 ge:
+// match + 2 ge, mismatch + 2 ge and 2 ge must have a zero low byte as half floats on top of what the row frame asks.  Its
+// values lie up to two ge further from the true scores (the second floor ge * (r + 2), the class-1 maximum in the frame of
+// row r + 1), so the range is the row frame's with two more ge of room: match * ncols + ge * (steps + 3) + gi <= 2040.
+// That covers the most negative value too, -ge * (G + 1) - gi in front of the window, as steps >= G.
+__host__ __device__ inline int sw16_pairframe_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
+  const int rf = sw16_rowframe_steps(match, mismatch, gap_init, gap_ext, ncols);
+  if (rf < 0) return -1;
+  const int ge = -gap_ext;
+  const int sc[2] = {match + 2 * ge, mismatch + 2 * ge};          // 2 ge: as ge
+  for (int k = 0; k < 2; k++) {
+    int a = sc[k] < 0 ? -sc[k] : sc[k];
+    while (a && !(a & 1)) a >>= 1;
+    if (a > 7) return -1;
+  }
+  if (ge == 0) return rf;
+  return rf >= 2 ? rf - 2 : -1;
+}
 // ncols: columns of the register tile (longest read of this instance)
 __device__ inline Sw16Par sw16_par(const MapPar &p, int ncols = 512) {
   Sw16Par s;
@@ -440,6 +459,10 @@ __device__ inline Sw16Par sw16_par(const MapPar &p, int ncols = 512) {
   s.hi_rn = f16_bits_of_int(-p.gap_ext) >> 8;
   { const uint32_t e = f16_bits_of_int(-p.gap_ext), o = f16_bits_of_int(p.gap_init - p.gap_ext);       // + ge, - (gi - ge)
     s.pge = us2{(unsigned short)e, (unsigned short)e}; s.ngo = us2{(unsigned short)o, (unsigned short)o}; }
+  s.pf_steps = s.fp ? sw16_pairframe_steps(p.match, p.mismatch, p.gap_init, p.gap_ext, ncols) : -1;
+  s.hi_pmatch = f16_bits_of_int(p.match - 2 * p.gap_ext) >> 8; s.hi_pmismatch = f16_bits_of_int(p.mismatch - 2 * p.gap_ext) >> 8;
+  s.hi_pn = f16_bits_of_int(-2 * p.gap_ext) >> 8;
+  { const uint32_t e = f16_bits_of_int(2 * p.gap_ext); s.nge2 = us2{(unsigned short)e, (unsigned short)e}; }      // - 2 ge
   const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
   s.mm4 = (uint32_t)((p.mismatch + bias) & 0xff) * 0x01010101u;      // a row of mismatches ...
   s.dlt = (uint32_t)(p.match - p.mismatch);                          // ... plus this at the byte of the matching base
@@ -640,6 +663,110 @@ __device__ inline uint32_t sw16r_core(const uint16_t *wrow, int nstep, const uin
   return (uint32_t)(int)(float)best.x | ((uint32_t)(int)(float)best.y << 16);
 }
 
+// The half-float sweep in a column-pair frame: a lane's column cc has class p = cc & 1, and a value of window row r in a
+// column of class p is kept as X + ge * (r + p).  E is as in the row frame, with the floor ge * (r + 1 + p).  F decays by
+// ge per column and the frame rises by ge from an even to an odd column, so there F(cc + 1) = max(F, T) with no add; from
+// an odd column to the next even one it is max(F, T) - 2 ge, and behind the lane's last column (to column 0 of the right
+// neighbour, same row) - ge * (1 + class of the last column).  The diagonal into an odd column changes frame by 2 ge (table
+// sw16_rowtab2p), into an even column cc >= 2 by nothing (the plain table), into column 0 by ge * (1 - class of the left
+// neighbour's last column): the row-frame table for odd C, the plain one for even C.  Columns beyond the read keep the
+// selector of the constant 0: a true 0, - ge or - 2 ge, never positive.  The running maximum is one register per class;
+// going to the next row the class-1 register holds the class-0 maximum as it is and the class-0 register, + 2 ge, the
+// class-1 maximum.  The floors ge * r, ge * (r + 1), ge * (r + 2) of a row share two values with the next row's, so one
+// add per row makes the new one; with four floor registers, four rows bring every register back to its role, and the
+// loop body is four rows with the roles written out (no register moves, and none for the diagonal of column 0 either).
+// Per cell pair: perm, add, max3, add, max3, max, half an add and 0.5 for the running maximum: 7 instructions.
+// sw16_pairframe_steps() says when every value stays within the exact integers.
+template <int G, int C>
+__device__ inline uint32_t sw16p_core(const uint16_t *wrow, int nstep, const uint32_t (&sel)[C], int g, const Sw16Par &sp,
+                                      const uint2 *rowtab2, const uint2 *rowtab2r, const uint2 *rowtab2p) {
+  constexpr int PL = (C - 1) & 1;                // class of the lane's last column
+  hf2 H[C], E[C];
+  const hf2 pge = __builtin_bit_cast(hf2, sp.pge), nge = __builtin_bit_cast(hf2, sp.nge), ngo = __builtin_bit_cast(hf2, sp.ngo);
+  const hf2 nge2 = __builtin_bit_cast(hf2, sp.nge2), pge2 = pge + pge;
+  const _Float16 r0 = (_Float16)(-g);
+  hf2 n0 = pge * hf2{r0, r0}, n1 = n0 + pge, n2 = n1 + pge, n3 = n2;  // floors of the row the lane does next (row -g at first)
+  // the row before the first: everything at the true 0 of the frame it is next read in
+  hf2 ma = n0 - pge, mb = n0;                    // maxima of class 0 and class 1 of the row done last
+  {
+#pragma unroll
+    for (int cc = 0; cc < C; cc++) { H[cc] = (cc & 1) ? mb : ma; E[cc] = (cc & 1) ? n1 : n0; }
+  }
+  hf2 F = ma, pa = PL ? mb : ma, pb = pa;        // pa / pb: H of the left neighbour's last column, one row back, in turn
+  const uint32_t gmask = g == 0 ? 0u : 0xffffffffu;      // the first lane of a group has no left neighbour: it takes the floors
+#define SW16P_SB() __builtin_amdgcn_sched_barrier(0)
+  // one row with floors f0, f1, f2; c0: the register that takes the class-0 maximum (it held class 1 of the row before),
+  // c1: the one that takes class 1 (it held class 0); carry: diagonal of column 0, hl: where the next row's goes
+  auto row = [&](int step, const hf2 f0, const hf2 f1, const hf2 f2, hf2 &c0, hf2 &c1, const hf2 carry, hf2 &hl) __attribute__((always_inline)) {
+    const uint32_t e = wrow[step - g + (G - 1)];
+    const uint2 rq = rowtab2[e], rp = rowtab2p[e];
+    const uint2 rz = PL ? rq : rowtab2r[e];
+    // the hand-over runs in every lane (a DPP read of a lane that a branch has switched off yields 0), then a bitwise select
+    const uint32_t f0b = __builtin_bit_cast(uint32_t, f0), fhb = __builtin_bit_cast(uint32_t, PL ? f1 : f0);
+    hl = __builtin_bit_cast(hf2, (shr1_u32(__builtin_bit_cast(uint32_t, H[C - 1])) & gmask) | (fhb & ~gmask));
+    F = __builtin_bit_cast(hf2, (shr1_u32(__builtin_bit_cast(uint32_t, F)) & gmask) | (f0b & ~gmask));
+    // As in sw16r_core: what does not depend on the F chain goes between its links (three on an even column, four on an
+    // odd one), and the order is pinned.
+    hf2 t3[C + 2];
+    t3[0] = carry + __builtin_bit_cast(hf2, __builtin_amdgcn_perm(rz.y, rz.x, sel[0]));
+    if (C > 1) t3[1] = H[0] + __builtin_bit_cast(hf2, __builtin_amdgcn_perm(rp.y, rp.x, sel[1]));
+    SW16P_SB();
+#pragma unroll
+    for (int cc = 0; cc < C; cc++) {
+      const bool odd = cc & 1;
+      const hf2 hh = hf_max3(t3[cc], E[cc], F);
+      SW16P_SB();
+      hf2 w = hh;
+      if (cc + 2 < C) w = __builtin_bit_cast(hf2, odd ? __builtin_amdgcn_perm(rp.y, rp.x, sel[cc + 2 < C ? cc + 2 : 0])
+                                                      : __builtin_amdgcn_perm(rq.y, rq.x, sel[cc + 2 < C ? cc + 2 : 0]));
+      SW16P_SB();
+      const hf2 tt = hh + ngo;
+      SW16P_SB();
+      if (cc + 2 < C) t3[cc + 2] = H[cc + 1 < C ? cc + 1 : 0] + w;
+      SW16P_SB();
+      const hf2 fm = __builtin_elementwise_maximum(F, tt);
+      SW16P_SB();
+      E[cc] = hf_max3(E[cc], tt, odd ? f2 : f1);
+      H[cc] = hh;
+      SW16P_SB();
+      if (cc == C - 1) F = fm + (PL ? nge2 : nge);
+      else if (odd) F = fm + nge2;
+      else F = fm;
+      SW16P_SB();
+      if (cc == 0) c1 = c1 + pge2;
+      hf2 &cm = odd ? c1 : c0;
+      if ((cc >> 1) & 1) cm = hf_max3(cm, H[cc - 2 >= 0 ? cc - 2 : 0], H[cc]);
+      else if (cc + 2 >= C) cm = __builtin_elementwise_maximum(cm, H[cc]);
+      SW16P_SB();
+    }
+  };
+  int step = 0;
+  // The four-row body takes some fifteen registers more than a single row (the compiler renames across the rows).  The
+  // 32-column tiling would go from three waves per SIMD to two with it, so it runs the single rows only.
+  if (C <= 20) for (; step + 3 < nstep; step += 4) {
+    row(step, n0, n1, n2, mb, ma, pa, pb);
+    n3 = n2 + pge;
+    row(step + 1, n1, n2, n3, ma, mb, pb, pa);
+    n0 = n3 + pge;
+    row(step + 2, n2, n3, n0, mb, ma, pa, pb);
+    n1 = n0 + pge;
+    row(step + 3, n3, n0, n1, ma, mb, pb, pa);
+    n2 = n1 + pge;
+  }
+  for (; step < nstep; step++) {                 // the up to three rows left, the roles kept by moves
+    row(step, n0, n1, n2, mb, ma, pa, pb);
+    { const hf2 t = ma; ma = mb; mb = t; }
+    pa = pb;
+    n0 = n1; n1 = n2; n2 = n2 + pge;
+  }
+#undef SW16P_SB
+  // true scores, per lane: ma is in the frame of the lane's last row (n0 - ge), mb in that of the row after it
+  hf2 best = __builtin_elementwise_maximum(ma - (n0 - pge), mb - n0);
+  for (int o = G / 2; o > 0; o >>= 1)
+    best = __builtin_elementwise_maximum(best, __builtin_bit_cast(hf2, (uint32_t)__shfl_xor((int)__builtin_bit_cast(uint32_t, best), o)));
+  return (uint32_t)(int)(float)best.x | ((uint32_t)(int)(float)best.y << 16);
+}
+
 // rowtab[code]: the four biased ACGT scores against reference code 0..7 (4, 5, 6: 'N' -> score 0; 7 decodes as A upstream)
 __device__ inline void sw16_rowtab(uint32_t *rowtab, const Sw16Par &sp) {
   if (threadIdx.x < 8) rowtab[threadIdx.x] = threadIdx.x < 4 ? sp.mm4 + (sp.dlt << (8 * threadIdx.x)) : sp.n4;
@@ -663,6 +790,13 @@ __device__ inline void sw16_rowtab2r(uint2 *rowtab2r, const Sw16Par &sp) {
   const uint32_t x4 = sp.hi_rmismatch * 0x01010101u, n4 = sp.hi_rn * 0x01010101u;
   rowtab2r[threadIdx.x] = make_uint2(a < 4 ? (x4 & ~(0xffu << (8 * a))) | (sp.hi_rmatch << (8 * a)) : n4,
                                      bq < 4 ? (x4 & ~(0xffu << (8 * bq))) | (sp.hi_rmatch << (8 * bq)) : n4);
+}
+// the third table, of the pair-frame form's odd columns: every score + 2 ge; N rows hold 2 ge (a true 0)
+__device__ inline void sw16_rowtab2p(uint2 *rowtab2p, const Sw16Par &sp) {
+  const uint32_t a = threadIdx.x & 7u, bq = threadIdx.x >> 3;
+  const uint32_t x4 = sp.hi_pmismatch * 0x01010101u, n4 = sp.hi_pn * 0x01010101u;
+  rowtab2p[threadIdx.x] = make_uint2(a < 4 ? (x4 & ~(0xffu << (8 * a))) | (sp.hi_pmatch << (8 * a)) : n4,
+                                     bq < 4 ? (x4 & ~(0xffu << (8 * bq))) | (sp.hi_pmatch << (8 * bq)) : n4);
 }
 enum : uint32_t { SW16_NPAIR = 5u | (5u << 3) };
 
@@ -793,7 +927,7 @@ __device__ inline void sw16_window(uint16_t *wrow, int g, uint32_t nent, const u
 }
 
 template <int G, int C, int WMAX>
-__global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p, uint32_t ntask_cap, int rowframe) {
+__global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p, uint32_t ntask_cap, int frames) {
   // the small-LDS instance (WMAX = SW_SHORT_WMAX) runs first; the large one only sees what is left
   // (through the list S7 made of them; if the list overflowed, by scanning all candidates)
   const unsigned long long nlong = WMAX > SW_SHORT_WMAX ? b.work[WK_LONG_TASKS] : 0;
@@ -801,14 +935,16 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
   const uint32_t *list = (WMAX > SW_SHORT_WMAX && b.long_list && nlong <= b.long_cap) ? b.long_list : nullptr;
   constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
   __shared__ __attribute__((aligned(16))) uint16_t win[NG][sw16_went(G, WMAX)];
-  __shared__ uint2 rowtab2[64], rowtab2r[64];
+  __shared__ uint2 rowtab2[64], rowtab2r[64], rowtab2p[64];
   __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t ntask = list ? (uint32_t)nlong : min(*b.rc_count, ntask_cap), npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
   sw16_rowtab2(rowtab2, sp);
-  const int rf_steps = rowframe ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
+  const int rf_steps = (frames & 1) ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
+  const int pf_steps = (frames & 2) ? sp.pf_steps : -1;      // and up to this many in the pair frame, which goes first
   if (rf_steps >= 0) sw16_rowtab2r(rowtab2r, sp);
+  if (pf_steps >= 0) sw16_rowtab2p(rowtab2p, sp);
   const uint32_t niter = (npair + NG - 1) / NG;                             // iterations of NG task pairs, dealt to the waves in turn
   const bool small = ix.totlen <= 0xffffffffull;
   const int64_t lastw = (int64_t)(ix.totlen / 10);
@@ -874,7 +1010,8 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
     uint32_t sel[C];
     sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
-    const uint32_t bb = nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)      // nstep is wave-uniform: a scalar branch
+    const uint32_t bb = nstep <= pf_steps ? sw16p_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2, rowtab2r, rowtab2p)      // nstep is wave-uniform: scalar branches
+                        : nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)
                         : sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
     if ((meta >> 25) & 1u) {                                               // lanes 0 and 1 with a task of their own that was scored
       const int best = (int)((bb >> (16 * g)) & 0xffffu);
@@ -893,18 +1030,20 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
 // brings a query of its own, so the selectors take one staging pass per task
 template <int G, int C>
 __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
-                                                       const uint32_t *r_off, uint32_t ntask, MapPar p, int32_t *scores, int rowframe) {
+                                                       const uint32_t *r_off, uint32_t ntask, MapPar p, int32_t *scores, int frames) {
   constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
   constexpr int WMAX = SW_FULL_WMAX;
   __shared__ uint16_t win[NG][WMAX + 2 * G];
-  __shared__ uint2 rowtab2[64], rowtab2r[64];
+  __shared__ uint2 rowtab2[64], rowtab2r[64], rowtab2p[64];
   __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
   sw16_rowtab2(rowtab2, sp);
-  const int rf_steps = rowframe ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
+  const int rf_steps = (frames & 1) ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
+  const int pf_steps = (frames & 2) ? sp.pf_steps : -1;      // and up to this many in the pair frame, which goes first
   if (rf_steps >= 0) sw16_rowtab2r(rowtab2r, sp);
+  if (pf_steps >= 0) sw16_rowtab2p(rowtab2p, sp);
   const uint32_t ngroups = gridDim.x * NG;
   for (uint32_t t0 = blockIdx.x * NG; t0 < npair; t0 += ngroups) {
     const uint32_t tp = t0 + grp;
@@ -951,7 +1090,8 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
     uint32_t sel[C];
     sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
-    const uint32_t bb = nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)      // nstep is wave-uniform: a scalar branch
+    const uint32_t bb = nstep <= pf_steps ? sw16p_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2, rowtab2r, rowtab2p)      // nstep is wave-uniform: scalar branches
+                        : nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)
                         : sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
     if (g == 0) {
 #pragma unroll
@@ -1623,21 +1763,27 @@ static bool sw16_ok(const MapPar &p) {
          -p.gap_init >= 0 && -p.gap_init < 30000 && -p.gap_ext >= 0 && -p.gap_ext < 30000;
 }
 
-// test hook: SMALTGPU_SW16_ROWFRAME=0 keeps the packed sweep in its forms without the row frame (sw16f_core, sw16_core), so
-// that both can be compared on the same tasks; read at every launch, which lets one process run both
-static int sw16_rowframe_on() {
+// test hooks: SMALTGPU_SW16_ROWFRAME=0 keeps the packed sweep in its forms without any frame (sw16f_core, sw16_core),
+// SMALTGPU_SW16_PAIRFRAME=0 gives the row frame wherever it applies, so that the forms can be compared on the same tasks;
+// read at every launch, which lets one process run all three.  Bit 0: row frame, bit 1: pair frame.
+static int sw16_frames_on() {
   const char *e = getenv("SMALTGPU_SW16_ROWFRAME");
-  return !(e && e[0] == '0');
+  if (e && e[0] == '0') return 0;
+  e = getenv("SMALTGPU_SW16_PAIRFRAME");
+  return (e && e[0] == '0') ? 1 : 3;
 }
 int sw16_rowframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
   return sw16_rowframe_steps(match, mismatch, gap_init, gap_ext, ncols);
+}
+int sw16_pairframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
+  return sw16_pairframe_steps(match, mismatch, gap_init, gap_ext, ncols);
 }
 
 template <int G, int C>
 static void launch_sw_full_t(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t ntask_cap, uint32_t grid) {
   const int use16 = sw16_ok(p);
   if (use16) {
-    const int rf = sw16_rowframe_on();
+    const int rf = sw16_frames_on();
     hipLaunchKernelGGL((k_sw_full16<G, C, SW_SHORT_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
     hipLaunchKernelGGL((k_sw_full16<G, C, SW_FULL_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
   }
@@ -1691,7 +1837,7 @@ int launch_sw_scalar(hipStream_t s, const Batch &b, const DevIndex &ix, const Ma
 template <int G, int C>
 static void launch_sw_raw_t(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n,
                             const MapPar &p, int32_t *sc, uint32_t grid, int packed16) {
-  if (packed16) hipLaunchKernelGGL((k_sw_full16_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc, sw16_rowframe_on());
+  if (packed16) hipLaunchKernelGGL((k_sw_full16_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc, sw16_frames_on());
   else hipLaunchKernelGGL((k_sw_full_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc);
 }
 
