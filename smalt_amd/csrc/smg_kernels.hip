@@ -392,6 +392,30 @@ __device__ inline us2 pk_max3(us2 a, us2 b, us2 c) {
   return __builtin_bit_cast(us2, r);
 }
 __device__ inline uint32_t shr1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, true); }
+// The two lane hand-overs of a sweep row, each with its select in the same instruction: h = first lane of its group ?
+// hfirst : hv of the lane to the left, f likewise from its own value one lane to the left.  v_cndmask_b32 is VOP2 and
+// takes a DPP source here: dst = VCC ? src1 : dpp(src0).  The compiler does not form it from update_dpp and a select (it
+// keeps a v_mov_b32_dpp and a v_cndmask_b32), hence the assembly.  What it rests on:
+//  * every lane is on: a DPP read of a lane that a branch has switched off yields 0, so this is never under a divergent
+//    branch (the sweeps run under wave-uniform, scalar branches only);
+//  * bound_ctrl: lane 0 of a DPP row of 16 has no source lane and takes 0 instead of skipping its write; it is the first
+//    lane of a group for G = 4, 8, 16, so VCC picks src1 there anyway;
+//  * a VALU write of a register needs two wait states before a DPP read of it, and the hazard pass does not look into
+//    inline assembly: the s_mov and the s_nop are those two for hv, whatever came before the block, and f has three;
+//  * VCC is set from the mask inside the block and listed as clobbered, so nothing can come between setting and use.
+template <int G>
+__device__ inline void shr1_first2_u32(uint32_t &h, uint32_t &f, uint32_t hv, uint32_t hfirst, uint32_t ffirst) {
+  static_assert(G == 4 || G == 8 || G == 16, "a group starts on lane 0 of every DPP row");
+  constexpr unsigned long long first = G == 4 ? 0x1111111111111111ull : G == 8 ? 0x0101010101010101ull : 0x0001000100010001ull;
+  asm volatile("s_mov_b64 vcc, %5\n\t"
+               "s_nop 0\n\t"
+               "v_cndmask_b32_dpp %0, %2, %3, vcc row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+               "v_cndmask_b32_dpp %1, %1, %4, vcc row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+               : "=&v"(h), "+v"(f) : "v"(hv), "v"(hfirst), "v"(ffirst), "s"(first) : "vcc");
+}
+// entry of a score table by byte offset (the window arrays hold code pair x 8): the LDS read takes the entry register
+// and the table's address as its immediate offset
+__device__ inline uint2 sw16_tab(const uint2 *tab, uint32_t e8) { return *(const uint2 *)((const char *)tab + e8); }
 
 enum : int { SW16_BLK = 5 };
 struct Sw16Par { uint32_t mm4, dlt, n4; us2 bias, gi, ge; int fp; uint32_t hi_match, hi_mismatch; us2 ngi, nge;
@@ -473,9 +497,10 @@ __device__ inline Sw16Par sw16_par(const MapPar &p, int ncols = 512) {
   return s;
 }
 
-// wrow: per-row code pairs (code of task A | code of task B << 3) of this lane group, entry r + G - 1 = row r; the
-// entries before row 0 and from the last row up to nstep + G - 1 hold the N pair, so the sweep reads without bounds checks.
-// rowtab2[pair]: the biased ACGT score rows of both codes (one 8-byte LDS read per row).
+// wrow: per-row code pairs (code of task A | code of task B << 3) of this lane group, each times 8 -- the byte offset of
+// the pair's entry in the score tables, at most 63 x 8 = 504; entry r + G - 1 = row r; the entries before row 0 and from
+// the last row up to nstep + G - 1 hold the N pair, so the sweep reads without bounds checks.
+// rowtab2[pair]: the biased ACGT score rows of both codes (one 8-byte LDS read per row, sw16_tab).
 template <int G, int C>
 __device__ inline uint32_t sw16_core(const uint16_t *wrow, int nstep, const uint32_t (&sel)[C], int g, const Sw16Par &sp, const uint2 *rowtab2) {
   us2 H[C], E[C];
@@ -483,8 +508,9 @@ __device__ inline uint32_t sw16_core(const uint16_t *wrow, int nstep, const uint
   for (int cc = 0; cc < C; cc++) { H[cc] = us2{0, 0}; E[cc] = us2{0, 0}; }
   us2 best = us2{0, 0}, F = us2{0, 0}, prev_hl = us2{0, 0};
   const uint32_t gmask = g == 0 ? 0u : 0xffffffffu;       // the first lane of a group has no left neighbour
-  for (int step = 0; step < nstep; step++) {
-    const uint2 rr = rowtab2[wrow[step - g + (G - 1)]];
+  const uint16_t *wp = wrow + (G - 1) - g;                // the lane's row pointer, one bump per row
+  for (int step = 0; step < nstep; step++, wp++) {
+    const uint2 rr = sw16_tab(rowtab2, *wp);
     const uint32_t rowA = rr.x, rowB = rr.y;                              // ACGT scores (+ bias) against this reference base
     const uint32_t hl = shr1_u32(as_u32(H[C - 1])) & gmask;
     const uint32_t fin = shr1_u32(as_u32(F)) & gmask;
@@ -544,8 +570,9 @@ __device__ inline uint32_t sw16f_core(const uint16_t *wrow, int nstep, const uin
   hf2 best = zero, F = zero, prev_hl = zero;
   const hf2 ngi = __builtin_bit_cast(hf2, sp.ngi), nge = __builtin_bit_cast(hf2, sp.nge);
   const uint32_t gmask = g == 0 ? 0u : 0xffffffffu;
-  for (int step = 0; step < nstep; step++) {
-    const uint2 rr = rowtab2[wrow[step - g + (G - 1)]];
+  const uint16_t *wp = wrow + (G - 1) - g;
+  for (int step = 0; step < nstep; step++, wp++) {
+    const uint2 rr = sw16_tab(rowtab2, *wp);
     const uint32_t hl = shr1_u32(__builtin_bit_cast(uint32_t, H[C - 1])) & gmask;
     const uint32_t fin = shr1_u32(__builtin_bit_cast(uint32_t, F)) & gmask;
     hf2 carry = prev_hl;
@@ -612,15 +639,15 @@ __device__ inline uint32_t sw16r_core(const uint16_t *wrow, int nstep, const uin
     for (int cc = 0; cc < C; cc++) { H[cc] = f0; E[cc] = flo1; }
   }
   hf2 best = flo1 - pge, F = best, prev_hl = best, flo = best;
-  const uint32_t gmask = g == 0 ? 0u : 0xffffffffu;      // the first lane of a group has no left neighbour: it takes flo
-  for (int step = 0; step < nstep; step++) {
-    const uint2 rr = rowtab2r[wrow[step - g + (G - 1)]];
+  const uint16_t *wp = wrow + (G - 1) - g;
+  for (int step = 0; step < nstep; step++, wp++) {
+    const uint2 rr = sw16_tab(rowtab2r, *wp);
     flo = flo1;
     flo1 = flo + pge;
     const uint32_t flob = __builtin_bit_cast(uint32_t, flo);
-    // the hand-over runs in every lane (a DPP read of a lane that a branch has switched off yields 0), then a bitwise select
-    const uint32_t hl = (shr1_u32(__builtin_bit_cast(uint32_t, H[C - 1])) & gmask) | (flob & ~gmask);
-    const uint32_t fin = (shr1_u32(__builtin_bit_cast(uint32_t, F)) & gmask) | (flob & ~gmask);
+    // the hand-over runs in every lane; the first lane of a group has no left neighbour: it takes flo (shr1_first2_u32)
+    uint32_t hl, fin = __builtin_bit_cast(uint32_t, F);
+    shr1_first2_u32<G>(hl, fin, __builtin_bit_cast(uint32_t, H[C - 1]), flob, flob);
     hf2 carry = prev_hl;
     prev_hl = __builtin_bit_cast(hf2, hl);
     F = __builtin_bit_cast(hf2, fin);
@@ -693,18 +720,20 @@ __device__ inline uint32_t sw16p_core(const uint16_t *wrow, int nstep, const uin
     for (int cc = 0; cc < C; cc++) { H[cc] = (cc & 1) ? mb : ma; E[cc] = (cc & 1) ? n1 : n0; }
   }
   hf2 F = ma, pa = PL ? mb : ma, pb = pa;        // pa / pb: H of the left neighbour's last column, one row back, in turn
-  const uint32_t gmask = g == 0 ? 0u : 0xffffffffu;      // the first lane of a group has no left neighbour: it takes the floors
+  const uint16_t *wp = wrow + (G - 1) - g;       // the lane's row pointer: entry r + G - 1 is row r, and the lane starts on row -g
 #define SW16P_SB() __builtin_amdgcn_sched_barrier(0)
   // one row with floors f0, f1, f2; c0: the register that takes the class-0 maximum (it held class 1 of the row before),
   // c1: the one that takes class 1 (it held class 0); carry: diagonal of column 0, hl: where the next row's goes
-  auto row = [&](int step, const hf2 f0, const hf2 f1, const hf2 f2, hf2 &c0, hf2 &c1, const hf2 carry, hf2 &hl) __attribute__((always_inline)) {
-    const uint32_t e = wrow[step - g + (G - 1)];
-    const uint2 rq = rowtab2[e], rp = rowtab2p[e];
-    const uint2 rz = PL ? rq : rowtab2r[e];
-    // the hand-over runs in every lane (a DPP read of a lane that a branch has switched off yields 0), then a bitwise select
-    const uint32_t f0b = __builtin_bit_cast(uint32_t, f0), fhb = __builtin_bit_cast(uint32_t, PL ? f1 : f0);
-    hl = __builtin_bit_cast(hf2, (shr1_u32(__builtin_bit_cast(uint32_t, H[C - 1])) & gmask) | (fhb & ~gmask));
-    F = __builtin_bit_cast(hf2, (shr1_u32(__builtin_bit_cast(uint32_t, F)) & gmask) | (f0b & ~gmask));
+  // k: the row's entry behind the lane's row pointer wp, which the loops bump (the body once for its four rows)
+  auto row = [&](int k, const hf2 f0, const hf2 f1, const hf2 f2, hf2 &c0, hf2 &c1, const hf2 carry, hf2 &hl) __attribute__((always_inline)) {
+    const uint32_t e = wp[k];
+    const uint2 rq = sw16_tab(rowtab2, e), rp = sw16_tab(rowtab2p, e);
+    const uint2 rz = PL ? rq : sw16_tab(rowtab2r, e);
+    // the hand-over runs in every lane; the first lane of a group has no left neighbour: it takes the floors (shr1_first2_u32)
+    uint32_t hlb, fb = __builtin_bit_cast(uint32_t, F);
+    shr1_first2_u32<G>(hlb, fb, __builtin_bit_cast(uint32_t, H[C - 1]), __builtin_bit_cast(uint32_t, PL ? f1 : f0), __builtin_bit_cast(uint32_t, f0));
+    hl = __builtin_bit_cast(hf2, hlb);
+    F = __builtin_bit_cast(hf2, fb);
     // As in sw16r_core: what does not depend on the F chain goes between its links (three on an even column, four on an
     // odd one), and the order is pinned.
     hf2 t3[C + 2];
@@ -743,18 +772,18 @@ __device__ inline uint32_t sw16p_core(const uint16_t *wrow, int nstep, const uin
   int step = 0;
   // The four-row body takes some fifteen registers more than a single row (the compiler renames across the rows).  The
   // 32-column tiling would go from three waves per SIMD to two with it, so it runs the single rows only.
-  if (C <= 20) for (; step + 3 < nstep; step += 4) {
-    row(step, n0, n1, n2, mb, ma, pa, pb);
+  if (C <= 20) for (; step + 3 < nstep; step += 4, wp += 4) {
+    row(0, n0, n1, n2, mb, ma, pa, pb);
     n3 = n2 + pge;
-    row(step + 1, n1, n2, n3, ma, mb, pb, pa);
+    row(1, n1, n2, n3, ma, mb, pb, pa);
     n0 = n3 + pge;
-    row(step + 2, n2, n3, n0, mb, ma, pa, pb);
+    row(2, n2, n3, n0, mb, ma, pa, pb);
     n1 = n0 + pge;
-    row(step + 3, n3, n0, n1, ma, mb, pb, pa);
+    row(3, n3, n0, n1, ma, mb, pb, pa);
     n2 = n1 + pge;
   }
-  for (; step < nstep; step++) {                 // the up to three rows left, the roles kept by moves
-    row(step, n0, n1, n2, mb, ma, pa, pb);
+  for (; step < nstep; step++, wp++) {           // the up to three rows left, the roles kept by moves
+    row(0, n0, n1, n2, mb, ma, pa, pb);
     { const hf2 t = ma; ma = mb; mb = t; }
     pa = pb;
     n0 = n1; n1 = n2; n2 = n2 + pge;
@@ -901,7 +930,7 @@ __device__ inline uint32_t sw16_codes10(const uint32_t *packed, int64_t wbase, u
   const uint32_t valid = ((1u << (3 * (10 - dlo))) - 1u) & ~((1u << (3 * (10 - dhi))) - 1u);
   return (sw16_map10(raw) & valid) | (SW16_N10 & ~valid);
 }
-// the window array of a lane group: entry e = row e - (G-1) as code of task A | code of task B << 3, N pairs around the windows
+// the window array of a lane group: entry e = row e - (G-1) as (code of task A | code of task B << 3) x 8, N pairs around the windows
 template <int G>
 __device__ inline void sw16_window(uint16_t *wrow, int g, uint32_t nent, const uint32_t *packed, int64_t lastw, const int64_t (&wbase)[2],
                                    const uint32_t (&ws)[2], const uint32_t (&wlen)[2]) {
@@ -921,7 +950,7 @@ __device__ inline void sw16_window(uint16_t *wrow, int g, uint32_t nent, const u
     for (int pr = 0; pr < 5; pr++) {
       const int s0 = 3 * (9 - 2 * pr), s1 = s0 - 3;
       const uint32_t e0 = ((ma >> s0) & 7u) | (((mb >> s0) & 7u) << 3), e1 = ((ma >> s1) & 7u) | (((mb >> s1) & 7u) << 3);
-      dst[5 * m + (uint32_t)pr] = e0 | (e1 << 16);
+      dst[5 * m + (uint32_t)pr] = (e0 | (e1 << 16)) << 3;                   // pair x 8 in either half (< 512: no carry across)
     }
   }
 }
@@ -935,7 +964,8 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
   const uint32_t *list = (WMAX > SW_SHORT_WMAX && b.long_list && nlong <= b.long_cap) ? b.long_list : nullptr;
   constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
   __shared__ __attribute__((aligned(16))) uint16_t win[NG][sw16_went(G, WMAX)];
-  __shared__ uint2 rowtab2[64], rowtab2r[64], rowtab2p[64];
+  // each on a multiple of its 512 bytes: the paired read of two tables (ds_read2st64) counts its offsets in units of 512
+  __shared__ __attribute__((aligned(512))) uint2 rowtab2[64], rowtab2r[64], rowtab2p[64];
   __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t ntask = list ? (uint32_t)nlong : min(*b.rc_count, ntask_cap), npair = (ntask + 1) / 2;
@@ -1034,7 +1064,8 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
   constexpr int NG = 64 / G, NW = Sw16Geo<G, C>::NW;
   constexpr int WMAX = SW_FULL_WMAX;
   __shared__ uint16_t win[NG][WMAX + 2 * G];
-  __shared__ uint2 rowtab2[64], rowtab2r[64], rowtab2p[64];
+  // each on a multiple of its 512 bytes: the paired read of two tables (ds_read2st64) counts its offsets in units of 512
+  __shared__ __attribute__((aligned(512))) uint2 rowtab2[64], rowtab2r[64], rowtab2p[64];
   __shared__ __attribute__((aligned(16))) uint8_t qst[2 * Sw16Geo<G, C>::QST];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t npair = (ntask + 1) / 2;
@@ -1069,7 +1100,7 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
       uint32_t cd[2];
 #pragma unroll
       for (int u = 0; u < 2; u++) { const uint32_t x = i < wlen[u] ? (r[u][i] & 7u) : 5u; cd[u] = x == 7 ? 0 : ((x == 6 || x == 4) ? 5 : x); }
-      win[grp][e] = (uint16_t)(cd[0] | (cd[1] << 3));
+      win[grp][e] = (uint16_t)((cd[0] | (cd[1] << 3)) << 3);                // pair x 8, as sw16_window writes it
     }
     uint32_t xa[NW], xb[NW];
 #pragma unroll
