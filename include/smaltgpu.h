@@ -406,10 +406,13 @@ int smaltgpu_map_split(smaltgpu_mapper *m, smaltgpu_post *post, const uint8_t *b
 /* Report: which alignments of a read are printed (resultSetFilterResults, results.c:2592; resultSetAddToReport, results.c:2282;
  * reportAddMap's duplicate test, report.c:545) and the lines themselves (fprintREPALIcigar report.c:711, fprintREPALIsam
  * report.c:762, writeDiffStrCIGAR diffstr.c:298, SAM header report.c:1266). */
-enum { SMALTGPU_FMT_CIGAR = 0, SMALTGPU_FMT_SAM = 1, SMALTGPU_FMT_SSAHA = 2 };           /* -f cigar | sam | ssaha (REPORTFMT_*, report.h:46-52; fprintREPALIssaha
-                                                                                          * report.c:579).  -f gff ends the reference program with a memory
-                                                                                          * fault on its first read (report.c:1389-1401 drops the block list
-                                                                                          * it has just made), -f bam needs a library this build has not */
+enum { SMALTGPU_FMT_CIGAR = 0, SMALTGPU_FMT_SAM = 1, SMALTGPU_FMT_SSAHA = 2, SMALTGPU_FMT_BAM = 3 };   /* -f cigar | sam | ssaha | bam (REPORTFMT_*, report.h:46-52;
+                                                                                          * fprintREPALIssaha report.c:579).  -f gff ends the reference program
+                                                                                          * with a memory fault on its first read (report.c:1389-1401 drops the
+                                                                                          * block list it has just made).  -f bam: the reference writes it through
+                                                                                          * the bambamc library (report.c:916-1081), which its build here lacks;
+                                                                                          * this library writes the records and their BGZF blocks itself, over
+                                                                                          * zlib (smg_bam.hpp).  BAM takes the modflags of SAM except ALIOUT */
 enum { SMALTGPU_REP_ALIOUT = 0x01, SMALTGPU_REP_SOFTCLIP = 0x02, SMALTGPU_REP_HEADER = 0x04, SMALTGPU_REP_XMISMATCH = 0x08 };   /* REPORTMODIF_* (report.h:54-59);
                                                                                           * ALIOUT (smalt map -a): the line of every mapped alignment, of any
                                                                                           * format, is followed by the alignment itself in blocks of three rows
@@ -441,6 +444,18 @@ int smaltgpu_report_emit(smaltgpu_report *rp, const smaltgpu_post_out *post, con
 int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pairs *pairs, const smaltgpu_reads_view *reads, const smaltgpu_reads_view *mates,
                                const char *const *seqnames, int64_t nseq, const smaltgpu_report_opts *op, const smaltgpu_pair_opts *po, int nthreads,
                                const char **text, uint64_t *len);
+/* SMALTGPU_FMT_BAM: the three calls above hand out whole BGZF blocks instead of text -- smaltgpu_report_header the magic, the SAM header
+ * text (empty without SMALTGPU_REP_HEADER) and the list of sequences (always), the emit functions one record per line the SAM format
+ * would have printed for the same modflags, in the same order: refID / next_refID are the places of RNAME / RNEXT in the sequence
+ * list (-1 for '*'), pos / next_pos the printed values - 1, the optional fields NM and AS as int32.  The records of a call are cut into
+ * payloads of 0xff00 bytes wherever that falls (a record may span blocks), the payloads are deflated on `nthreads` threads and every
+ * call ends its last block, so the bytes depend neither on the number of threads nor on an earlier call.  The deflate level is
+ * zlib's default, or SMALTGPU_BAM_LEVEL (0..9) as the environment has it when the report is created.  A read name longer than 254
+ * bytes or an alignment of more than 65535 CIGAR operations fails the emit call with SMALTGPU_EARG (the message names the read);
+ * SMALTGPU_REP_ALIOUT fails all three calls with SMALTGPU_EARG.
+ * smaltgpu_report_finish: what ends the output -- for SMALTGPU_FMT_BAM the 28-byte empty block that marks the end of a BAM file, for
+ * the text formats nothing (len 0).  Header, emit outputs and this, written one behind the other, are a complete BAM file. */
+int smaltgpu_report_finish(smaltgpu_report *rp, const smaltgpu_report_opts *op, const char **text, uint64_t *len);
 /* ---- insert-size histograms: `smalt sample` and `smalt map -g <file>` (insert.c; host code, smg_inshist.cpp) -------------------
  * `smalt sample` maps every n-th pair of a library, takes the template length of each pair whose two best alignments have a
  * mapping quality of at least 20 (resultSetInferInsertSize, results.c:2460; smalt.c:1180-1182, :850-854) and writes the histogram

@@ -89,7 +89,7 @@ class ReportOpts(C.Structure):         # smaltgpu_report_opts
                 ("min_swscor_below_max", C.c_int32), ("min_identity", C.c_double)]
 
 
-FMT_CIGAR, FMT_SAM, FMT_SSAHA = 0, 1, 2
+FMT_CIGAR, FMT_SAM, FMT_SSAHA, FMT_BAM = 0, 1, 2, 3
 REP_ALIOUT, REP_SOFTCLIP, REP_HEADER, REP_XMISMATCH = 0x01, 0x02, 0x04, 0x08
 OUT_BEST, OUT_SINGLE, OUT_SPLIT, OUT_RANDSEL = 0x01, 0x02, 0x04, 0x08
 
@@ -208,6 +208,7 @@ def lib():
         L.smaltgpu_index_packed_host.argtypes = [C.c_void_p]
         L.smaltgpu_report_set_reference.argtypes = [C.c_void_p, C.c_void_p]      # the packed host copy (smaltgpu_index_packed_host) for REP_ALIOUT
         L.smaltgpu_report_pair_inserts.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32)]
+        L.smaltgpu_report_finish.argtypes = [C.c_void_p, C.POINTER(ReportOpts), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]      # FMT_BAM: the end-of-file block
         _lib = L
     return _lib
 

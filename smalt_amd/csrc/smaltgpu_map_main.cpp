@@ -48,7 +48,8 @@ const char VERSION[] = "0.2";
 void usage() {
   fprintf(stderr,
           "usage: smaltgpu-map [options] <index prefix> <reads.fq|reads.fa>[.gz] [<mates.fq|mates.fa>[.gz]]\n"
-          "  -f <fmt>   cigar (default) | ssaha | sam | samsoft, SAM modifiers behind a colon: nohead, clip, x (e.g. sam:nohead,x)\n"
+          "  -f <fmt>   cigar (default) | ssaha | sam | samsoft | bam, SAM modifiers behind a colon: nohead, clip, x (e.g. sam:nohead,x);\n"
+          "             bam: the SAM records in binary (BGZF blocks, deflate level SMALTGPU_BAM_LEVEL=0..9), same modifiers (e.g. bam:x)\n"
           "  -o <file>  output file (default: standard output)\n"
           "  -m <int>   minimum Smith-Waterman score (default: word length + step - 1)\n"
           "  -d <int>   report alignments within <int> of the best score; -1: all (default 0: best only)\n"
@@ -275,6 +276,10 @@ int main(int argc, char **argv) {
   const char *prefix = argv[a], *readfil = argv[a + 1], *matefil = argc - a == 3 ? argv[a + 2] : nullptr;
   const bool paired = matefil != nullptr;
   if (paired && ins_min > ins_max) die("-j above -i");
+  if (!strncmp(fmt, "bam", 3) && (!fmt[3] || fmt[3] == ':')) {                             // binary output: nothing else may go into it
+    if (aliout) die("-a does not go with -f bam: a BAM file has no place for alignment blocks");
+    if (histfil && !oufil) die("-I with -f bam needs -o <file>: the two histogram prints go to standard output");
+  }
   smaltgpu_inshist *hist = nullptr;
   if (histfil) {                                                                         // smalt.c:556-571
     if (smaltgpu_inshist_read(&hist, histfil)) die("-I", smaltgpu_last_error());
@@ -299,9 +304,10 @@ int main(int argc, char **argv) {
     if (key == "cigar") ro.format = SMALTGPU_FMT_CIGAR;
     else if (key == "sam" || key == "samsoft") { ro.format = SMALTGPU_FMT_SAM; ro.modflags = SMALTGPU_REP_HEADER | SMALTGPU_REP_SOFTCLIP; }
     else if (key == "ssaha") ro.format = SMALTGPU_FMT_SSAHA;
-    else die("output format not supported here (cigar, sam, samsoft, ssaha)", fmt);
+    else if (key == "bam") { ro.format = SMALTGPU_FMT_BAM; ro.modflags = SMALTGPU_REP_HEADER | SMALTGPU_REP_SOFTCLIP; }      // menu.c:1009-1012: the SAM modifiers
+    else die("output format not supported here (cigar, sam, samsoft, ssaha, bam)", fmt);
     size_t p = f.find(':');
-    while (p != std::string::npos && ro.format == SMALTGPU_FMT_SAM) {
+    while (p != std::string::npos && (ro.format == SMALTGPU_FMT_SAM || ro.format == SMALTGPU_FMT_BAM)) {
       const size_t e = f.find(',', p + 1);
       const std::string mod = f.substr(p + 1, e == std::string::npos ? std::string::npos : e - p - 1);
       if (mod == "nohead") ro.modflags &= ~(uint32_t)SMALTGPU_REP_HEADER;
@@ -623,6 +629,11 @@ int main(int argc, char **argv) {
     }
     if (failure.empty() && fwrite(tail.data(), 1, tail.size(), ou) != tail.size()) failure = "write error";
     smaltgpu_inshist_free(sh);
+  }
+  if (!failed && failure.empty()) {                         // what ends the output (-f bam: the end-of-file block)
+    const char *t; uint64_t tl;
+    if (smaltgpu_report_finish(rep, &ro, &t, &tl)) failure = why("cannot end the output");
+    else if (tl && fwrite(t, 1, tl, ou) != tl) failure = "write error";
   }
   smaltgpu_report_free(rep);
   smaltgpu_inshist_free(hist);

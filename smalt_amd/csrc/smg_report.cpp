@@ -21,11 +21,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/smaltgpu.h"
+#include "smg_bam.hpp"
 
 extern "C" int smaltgpu_set_error(int code, const char *msg);   // smaltgpu.cpp: the per-thread message of smaltgpu_last_error()
 
@@ -554,7 +556,10 @@ bool print_ssaha_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &
   return true;
 }
 
-bool print_sam_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a, const PairSide *ps = nullptr) {        // fprintREPALIsam (report.c:762-906)
+// the places of RNAME and RNEXT of a SAM line in the sequence list (-1: '*'), for the binary form of the line (SMALTGPU_FMT_BAM)
+struct SamRefIds { int32_t ref = -1, next = -1; };
+
+bool print_sam_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a, const PairSide *ps = nullptr, SamRefIds *ids = nullptr) {        // fprintREPALIsam (report.c:762-906)
   char buf[96];
   const smaltgpu_report_opts &op = *cx.op;
   const bool mapped = (a.status & MF_MAPPED) != 0, soft = (op.modflags & SMALTGPU_REP_SOFTCLIP) != 0;
@@ -576,6 +581,7 @@ bool print_sam_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a,
       if (ps->mate->status & MF_REVERSE) flag |= 0x20;
       if (ps->mate->sidx < 0 || ps->mate->sidx >= cx.nseq) return false;
       mate_seq = cx.seqnames[ps->mate->sidx];
+      if (ids) ids->next = ps->mate->sidx;
     } else { flag |= 0x8; isize = 0; }
   }
   uint32_t seg0 = 0, segn = 0;
@@ -592,7 +598,7 @@ bool print_sam_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a,
   } else { flag |= 0x4; isize = 0; }
   snprintf(buf, sizeof(buf), "\t%hu\t", (unsigned short)flag);
   o += buf;
-  if (mapped) { if (a.sidx < 0 || a.sidx >= cx.nseq) return false; first_word(o, cx.seqnames[a.sidx], false); }
+  if (mapped) { if (a.sidx < 0 || a.sidx >= cx.nseq) return false; first_word(o, cx.seqnames[a.sidx], false); if (ids) ids->ref = a.sidx; }
   else o.push_back('*');
   snprintf(buf, sizeof(buf), "\t%i\t%hi\t", mapped ? (int)(uint32_t)a.ss : 0, (short)(mapped ? a.mapscor : 0));
   o += buf;
@@ -631,7 +637,7 @@ bool print_sam_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a,
 
 bool print_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a, const PairSide *ps) {       // writeREPALI's switch (report.c:1178-1200)
   switch (cx.op->format) {
-    case SMALTGPU_FMT_SAM: return print_sam_line(o, cx, i, a, ps);
+    case SMALTGPU_FMT_SAM: return print_sam_line(o, cx, i, a, ps);      // (SMALTGPU_FMT_BAM: print_entry)
     case SMALTGPU_FMT_SSAHA: return print_ssaha_line(o, cx, i, a, ps);
     default: return print_cigar_line(o, cx, i, a, ps);
   }
@@ -646,7 +652,10 @@ bool print_line(std::string &o, const ReadCtx &cx, uint32_t i, const Ali &a, con
 enum { ALI_WIDTH = 60 };                                   // DEFAULT_LINWIDTH_ALI (report.c:50); no option sets another
 enum : char { ALI_SAME = ' ', ALI_GAP = '-', ALI_TRANSITION = 'i', ALI_TRANSVERSION = 'v', ALI_UNKNOWN = '?', ALI_NONSTANDARD = '!' };   // report.c:100-105
 
-struct AliRows { std::string read, mark, ref; };           // scratch of one formatting thread
+struct AliRows {                                           // scratch of one formatting thread
+  std::string read, mark, ref;
+  std::string line, refused;                               // SMALTGPU_FMT_BAM: the SAM line of the record in the making; why a record cannot be made
+};
 
 // marker of a substitution column from the classes of its two letters (seqCodecFindBaseClass, sequence.c:441-452): A and G are purines,
 // C and T pyrimidines, every other letter counts as unknown, the end of a string as non-standard
@@ -733,6 +742,18 @@ bool put_alignment_blocks(std::string &o, AliRows &w, const ReadCtx &cx, uint32_
 
 // the line of an alignment and, with SMALTGPU_REP_ALIOUT, the blocks of a mapped one behind it (writeReportForRead, report.c:1486-1534)
 bool print_entry(std::string &o, AliRows &w, const ReadCtx &cx, uint32_t i, const Ali &a, const PairSide *ps) {
+  if (cx.op->format == SMALTGPU_FMT_BAM) {                   // the record is the SAM line in binary form (smg_bam.hpp)
+    SamRefIds ids;
+    w.line.clear();
+    if (!print_sam_line(w.line, cx, i, a, ps, &ids)) return false;
+    const int rv = smgbam::record_of_sam_line(o, w.line.data(), w.line.size(), ids.ref, ids.next);
+    if (rv == smgbam::NAME_TOO_LONG || rv == smgbam::TOO_MANY_OPS) {
+      w.refused = "read '";
+      w.refused.append(w.line, 0, std::min<size_t>(w.line.find('\t'), 300));
+      w.refused += rv == smgbam::NAME_TOO_LONG ? "': a BAM record holds a read name of at most 254 bytes" : "': a BAM record holds at most 65535 CIGAR operations";
+    }
+    return rv == smgbam::OK;
+  }
   if (!print_line(o, cx, i, a, ps)) return false;
   if (!(cx.op->modflags & SMALTGPU_REP_ALIOUT) || !(a.status & MF_MAPPED)) return true;
   return put_alignment_blocks(o, w, cx, i, a);
@@ -747,16 +768,38 @@ struct smaltgpu_report {
   const uint32_t *packed = nullptr;                                // smaltgpu_report_set_reference (borrowed)
   std::vector<int32_t> insert_size; std::vector<uint8_t> insert_known;      // per pair of the last smaltgpu_report_emit_pairs
   uint32_t npairs_emitted = 0;
+  std::string bam;                                                 // SMALTGPU_FMT_BAM: the BGZF blocks handed out
+  int bam_level = smgbam::level_of(getenv("SMALTGPU_BAM_LEVEL"));  // read once, when the report is made
 };
 
 namespace {
+inline bool sam_like(int32_t format) { return format == SMALTGPU_FMT_SAM || format == SMALTGPU_FMT_BAM; }
+
 int check_format(const smaltgpu_report *rp, const smaltgpu_report_opts *op, int64_t nseq) {
-  if (op->format != SMALTGPU_FMT_CIGAR && op->format != SMALTGPU_FMT_SAM && op->format != SMALTGPU_FMT_SSAHA) return smaltgpu_set_error(SMALTGPU_EARG, "unknown output format");
+  if (op->format != SMALTGPU_FMT_CIGAR && op->format != SMALTGPU_FMT_SAM && op->format != SMALTGPU_FMT_SSAHA && op->format != SMALTGPU_FMT_BAM)
+    return smaltgpu_set_error(SMALTGPU_EARG, "unknown output format");
+  if (op->format == SMALTGPU_FMT_BAM && (op->modflags & SMALTGPU_REP_ALIOUT))
+    return smaltgpu_set_error(SMALTGPU_EARG, "a BAM file has no place for alignment blocks: SMALTGPU_REP_ALIOUT goes with the text formats only");
   if (op->format == SMALTGPU_FMT_SSAHA && (int64_t)rp->seqlen.size() != nseq)
     return smaltgpu_set_error(SMALTGPU_EARG, "SSAHA lines carry the sequence lengths: call smaltgpu_report_header on this report first");
   if ((op->modflags & SMALTGPU_REP_ALIOUT) && (!rp->packed || (int64_t)rp->seqoff.size() != nseq + 1))
     return smaltgpu_set_error(SMALTGPU_EARG, "alignment blocks (SMALTGPU_REP_ALIOUT) show the reference: call smaltgpu_report_header and smaltgpu_report_set_reference on this report first");
   return SMALTGPU_OK;
+}
+
+// SMALTGPU_FMT_BAM: the uncompressed bytes of a call (header or records) leave as whole BGZF blocks; nothing stays behind for the next call
+int hand_out_bam(smaltgpu_report *rp, const std::string &plain, int nthreads, const char **text, uint64_t *len) {
+  rp->bam.clear();
+  if (!smgbam::bgzf(rp->bam, plain.data(), plain.size(), rp->bam_level, nthreads)) return smaltgpu_set_error(SMALTGPU_EINTERNAL, "BAM output: deflate failed");
+  *text = rp->bam.data(); *len = rp->bam.size();
+  return SMALTGPU_OK;
+}
+
+// a sequence name as the SAM header spells it: its first word, 511 characters at most
+std::string header_name(const char *n) {
+  std::string o;
+  for (int k = 0; k < 511 && n[k] && !isspace((unsigned char)n[k]); k++) o.push_back(n[k]);
+  return o;
 }
 }  // namespace
 
@@ -771,18 +814,25 @@ extern "C" int smaltgpu_report_header(smaltgpu_report *rp, const char *const *se
   rp->seqlen.resize((size_t)nseq);
   for (int64_t s = 0; s < nseq; s++) rp->seqlen[(size_t)s] = (uint32_t)(sop[s + 1] - sop[s]);
   rp->seqoff.assign(sop, sop + nseq + 1);
-  if (op->format == SMALTGPU_FMT_SAM && (op->modflags & SMALTGPU_REP_HEADER)) {       // writeSAMHeaderf (report.c:1266-1300)
+  if (op->format == SMALTGPU_FMT_BAM && (op->modflags & SMALTGPU_REP_ALIOUT)) return check_format(rp, op, nseq);
+  if (sam_like(op->format) && (op->modflags & SMALTGPU_REP_HEADER)) {       // writeSAMHeaderf (report.c:1266-1300)
     char buf[64];
     o += "@HD\tVN:1.3\tSO:unknown\n";
     for (int64_t s = 0; s < nseq; s++) {
       o += "@SQ\tSN:";
-      const char *n = seqnames[s];
-      for (int k = 0; k < 511 && n[k] && !isspace((unsigned char)n[k]); k++) o.push_back(n[k]);
+      o += header_name(seqnames[s]);
       snprintf(buf, sizeof(buf), "\tLN:%u\n", (unsigned)(sop[s + 1] - sop[s]));
       o += buf;
     }
     o += "@PG\tID:"; o += prognam ? prognam : "smaltgpu"; o += "\tPN:"; o += prognam ? prognam : "smaltgpu"; o += "\tVN:"; o += version ? version : "0"; o += "\tCL:";
     if (argc > 0 && argv) { for (int k = 0; k < argc; k++) { if (k) o.push_back(' '); o += argv[k]; } o.push_back('\n'); }
+  }
+  if (op->format == SMALTGPU_FMT_BAM) {                    // the same text (empty without the flag) and, always, the sequence list in binary
+    std::vector<std::string> names;
+    for (int64_t s = 0; s < nseq; s++) names.push_back(header_name(seqnames[s]));
+    std::string plain;
+    smgbam::header(plain, o.data(), o.size(), names, rp->seqlen.data());
+    return hand_out_bam(rp, plain, 1, text, len);
   }
   *text = o.data(); *len = o.size();
   return SMALTGPU_OK;
@@ -812,9 +862,11 @@ extern "C" int smaltgpu_report_emit(smaltgpu_report *rp, const smaltgpu_post_out
   rp->draw.assign(n ? n : 1, -1);
   for (uint32_t i = 0; i < n; i++) { const int ns = draw_range(cx, i); if (ns) rp->draw[i] = (int)(short)(drand48() * ns); }
   if (nthreads < 1) nthreads = 1;
+  const int nthreads_given = nthreads;
   if ((uint32_t)nthreads > n / 512 + 1) nthreads = (int)(n / 512 + 1);
   rp->part.resize((size_t)nthreads);
   std::vector<int> bad((size_t)nthreads, -1);
+  std::vector<std::string> refused((size_t)nthreads);
   auto work = [&](int t) {
     std::string &o = rp->part[(size_t)t];
     o.clear();
@@ -822,24 +874,30 @@ extern "C" int smaltgpu_report_emit(smaltgpu_report *rp, const smaltgpu_post_out
     std::vector<uint32_t> st;
     AliRows rows;
     const uint32_t lo = (uint32_t)((uint64_t)n * (uint64_t)t / (uint64_t)nthreads), hi = (uint32_t)((uint64_t)n * (uint64_t)(t + 1) / (uint64_t)nthreads);
-    o.reserve((size_t)(hi - lo) * ((op->format == SMALTGPU_FMT_SAM ? 420 : 96) + ((op->modflags & SMALTGPU_REP_ALIOUT) ? 640 : 0)));
+    o.reserve((size_t)(hi - lo) * ((sam_like(op->format) ? 420 : 96) + ((op->modflags & SMALTGPU_REP_ALIOUT) ? 640 : 0)));
     for (uint32_t i = lo; i < hi; i++) {
       if (!select_read(cx, i, rp->draw[i], alis, st)) { bad[(size_t)t] = (int)i; return; }
       for (const Ali &a : alis) {
         const bool ok = print_entry(o, rows, cx, i, a, nullptr);
-        if (!ok) { bad[(size_t)t] = (int)i; return; }
+        if (!ok) { bad[(size_t)t] = (int)i; refused[(size_t)t] = rows.refused; return; }
       }
     }
   };
   if (nthreads == 1) work(0);
   else { std::vector<std::thread> th; for (int t = 0; t < nthreads; t++) th.emplace_back(work, t); for (auto &x : th) x.join(); }
+  for (int t = 0; t < nthreads; t++) if (!refused[(size_t)t].empty()) return smaltgpu_set_error(SMALTGPU_EARG, refused[(size_t)t].c_str());
   for (int t = 0; t < nthreads; t++) if (bad[(size_t)t] >= 0) { char m[96]; snprintf(m, sizeof(m), "inconsistent alignment of read %d (alignment string or sequence number)", bad[(size_t)t]); return smaltgpu_set_error(SMALTGPU_EINTERNAL, m); }
-  if (nthreads == 1) { *text = rp->part[0].data(); *len = rp->part[0].size(); return SMALTGPU_OK; }
+  if (nthreads == 1) {
+    if (op->format == SMALTGPU_FMT_BAM) return hand_out_bam(rp, rp->part[0], nthreads_given, text, len);
+    *text = rp->part[0].data(); *len = rp->part[0].size();
+    return SMALTGPU_OK;
+  }
   rp->text.clear();
   size_t tot = 0;
   for (const std::string &s : rp->part) tot += s.size();
   rp->text.reserve(tot);
   for (const std::string &s : rp->part) rp->text += s;
+  if (op->format == SMALTGPU_FMT_BAM) return hand_out_bam(rp, rp->text, nthreads_given, text, len);
   *text = rp->text.data(); *len = rp->text.size();
   return SMALTGPU_OK;
 }
@@ -1001,6 +1059,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
   rp->insert_known.assign(n ? n : 1, 0);
   rp->npairs_emitted = n;
   if (nthreads < 1) nthreads = 1;
+  const int nthreads_given = nthreads;
   if ((uint32_t)nthreads > n / 256 + 1) nthreads = (int)(n / 256 + 1);
   const bool drawing = (op->outflags & SMALTGPU_OUT_RANDSEL) != 0;
   // pass 1: every pair that needs no random number is printed; the others say how many they need
@@ -1009,6 +1068,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
   std::vector<uint8_t> need(n ? n : 1, 0);
   rp->part.assign((size_t)nthreads + 1, std::string());
   std::vector<int64_t> bad((size_t)nthreads, -1);
+  std::vector<std::string> refused((size_t)nthreads + 1);
   auto pass = [&](int t, uint32_t lo, uint32_t hi, bool second, const std::vector<uint32_t> *todo, const std::vector<double> *values, const std::vector<uint64_t> *value_at) {
     std::string &o = rp->part[(size_t)t];
     Table A, B;
@@ -1023,7 +1083,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
       if (!pair_entries(jb, p, A, B, join, entries, dr)) { if (bad[(size_t)t] < 0) bad[(size_t)t] = p; continue; }
       if (!second && drawing && dr.used > 0) { need[p] = (uint8_t)dr.used; continue; }
       const uint64_t at = o.size();
-      if (!pair_lines(o, jb, p, A, B, entries, sh, rows)) { if (bad[(size_t)t] < 0) bad[(size_t)t] = p; continue; }
+      if (!pair_lines(o, jb, p, A, B, entries, sh, rows)) { if (bad[(size_t)t] < 0) { bad[(size_t)t] = p; refused[(size_t)t] = rows.refused; } continue; }
       where[p] = Slice{(uint32_t)t, at, o.size() - at};
       rp->insert_known[p] = sampled_insert(A, B, &rp->insert_size[p]) ? 1 : 0;
     }
@@ -1032,7 +1092,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; t++) {
       const uint32_t lo = (uint32_t)((uint64_t)n * t / nthreads), hi = (uint32_t)((uint64_t)n * (t + 1) / nthreads);
-      rp->part[(size_t)t].reserve((size_t)(hi - lo) * ((op->format == SMALTGPU_FMT_SAM ? 840 : 192) + ((op->modflags & SMALTGPU_REP_ALIOUT) ? 1280 : 0)));
+      rp->part[(size_t)t].reserve((size_t)(hi - lo) * ((sam_like(op->format) ? 840 : 192) + ((op->modflags & SMALTGPU_REP_ALIOUT) ? 1280 : 0)));
       if (nthreads == 1) pass(0, lo, hi, false, nullptr, nullptr, nullptr); else th.emplace_back(pass, t, lo, hi, false, nullptr, nullptr, nullptr);
     }
     for (std::thread &x : th) x.join();
@@ -1054,6 +1114,7 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
       pass(t, 0, (uint32_t)todo.size(), true, &todo, &values, &value_at);
     }
   }
+  for (const std::string &why : refused) if (!why.empty()) return smaltgpu_set_error(SMALTGPU_EARG, why.c_str());
   for (int64_t b : bad) if (b >= 0) { char m[128]; snprintf(m, sizeof(m), "smaltgpu_report_emit_pairs: pair %lld: inconsistent alignment sets or alignment strings", (long long)b); return smaltgpu_set_error(SMALTGPU_EINTERNAL, m); }
   // stitch in pair order
   size_t tot = 0;
@@ -1061,7 +1122,16 @@ extern "C" int smaltgpu_report_emit_pairs(smaltgpu_report *rp, const smaltgpu_pa
   rp->text.clear();
   rp->text.reserve(tot);
   for (uint32_t p = 0; p < n; p++) rp->text.append(rp->part[where[p].part], where[p].at, where[p].len);
+  if (op->format == SMALTGPU_FMT_BAM) return hand_out_bam(rp, rp->text, nthreads_given, text, len);
   *text = rp->text.data(); *len = rp->text.size();
+  return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_report_finish(smaltgpu_report *rp, const smaltgpu_report_opts *op, const char **text, uint64_t *len) {
+  if (!rp || !op || !text || !len) return smaltgpu_set_error(SMALTGPU_EARG, "smaltgpu_report_finish: null argument");
+  rp->bam.clear();
+  if (op->format == SMALTGPU_FMT_BAM) rp->bam.assign((const char *)smgbam::END_OF_FILE, sizeof(smgbam::END_OF_FILE));      // the empty block that ends a BAM file
+  *text = rp->bam.data(); *len = rp->bam.size();
   return SMALTGPU_OK;
 }
 
