@@ -394,6 +394,43 @@ void smaltgpu_reads_free(smaltgpu_reads *rs);
 int smaltgpu_reads_parse(smaltgpu_reads *rs, const char *text, uint64_t len, int is_last, uint32_t max_reads, int nthreads,
                          smaltgpu_reads_view *view);
 
+/* ---- reads from SAM and BAM files (smalt map -F sam|bam; host code, smg_alnin.hpp / smg_alnin.cpp) ------------------------------
+ * The reference reads such files through the bambamc library when it is linked with it (infmt.c; smalt.c:584 opens the file,
+ * :804-826 loads reads and mates of a template into the buffers, :1129-1184 sends a pair to rmapPair and anything else to
+ * rmapSingle, template by template); its build here lacks the library, and so does this one: the records and their BGZF blocks are
+ * read here, over zlib.  Single reads and pairs may be mixed in one file.  The rules are this project's (the order of bambamc's
+ * collator is not in the reference tree); smg_alnin.hpp states them in full:
+ *   - only QNAME, FLAG, SEQ and QUAL are used; records with flag 0x100 or 0x800 are dropped, every other record is one read;
+ *   - flag 0x10: the read is turned back into the strand it was sequenced in (IUPAC-aware complement, qualities reversed); letters
+ *     then as smaltgpu_reads_parse stores them; BAM qualities of 0xFF / SAM '*': the read has none, and BOTH views of a run that
+ *     holds such a read have has_qual = 0; a record without sequence is a read of no bases;
+ *   - flag 0x1 with exactly one of 0x40 / 0x80: a mate, named QNAME/1 or QNAME/2; it waits in a table (in memory) keyed by QNAME
+ *     until the other mate arrives from anywhere in the input; the pair takes the place of its later record, mate 1 is the read
+ *     and mate 2 the mate.  A record whose name and mate number already wait releases the waiting one as a single read at that
+ *     point.  What waits at the end follows as single reads in input order.  Everything else is a single read named QNAME.
+ * smaltgpu_alnreads_feed: `bytes[0..len)` are the next bytes of the file from where the last call stopped; *consumed says how far
+ * they were used (whole SAM lines, whole BGZF blocks): call again from there, with more bytes when nothing was consumed;
+ * is_last != 0: nothing follows `bytes` (a last line without newline is taken, a truncated block or record is an error, waiting
+ * mates are released).  BGZF blocks are inflated on `nthreads` threads.
+ * smaltgpu_alnreads_take: the next run of templates of ONE kind, at most max_templates (0: no limit): *kind 0 = none ready (feed
+ * more, or the end), 1 = single reads (`reads` only), 2 = pairs (read i of `reads` with read i of `mates`).  Runs are maximal
+ * stretches of consecutive templates of one kind and come in template order.  The views are filled as smaltgpu_reads_parse
+ * fills them (consumed = 0) and hold until the next take on this reader.
+ * Errors: SMALTGPU_EARG (null pointers, an unknown format, bytes behind is_last) or SMALTGPU_EFILE with a message that names the
+ * byte offset of the BGZF block in the file or the number of the record (from 1): a bad BGZF header, a wrong BSIZE, CRC or ISIZE
+ * mismatch, a block_size that runs past the data, l_read_name 0, a name without its NUL, a truncated last record, a SAM line of
+ * fewer than 11 fields, a SAM FLAG that is not a number, SEQ and QUAL of different lengths.  A reader that has failed repeats its
+ * error; it can be freed. */
+enum { SMALTGPU_IN_SAM = 1, SMALTGPU_IN_BAM = 2 };
+typedef struct smaltgpu_alnreads smaltgpu_alnreads;
+smaltgpu_alnreads *smaltgpu_alnreads_create(int format);     /* NULL: unknown format, or no memory */
+void smaltgpu_alnreads_free(smaltgpu_alnreads *r);
+int smaltgpu_alnreads_feed(smaltgpu_alnreads *r, const char *bytes, uint64_t len, int is_last, int nthreads, uint64_t *consumed);
+int smaltgpu_alnreads_take(smaltgpu_alnreads *r, uint32_t max_templates, int *kind, smaltgpu_reads_view *reads, smaltgpu_reads_view *mates);
+/* wall time [s] the reader has spent so far: BGZF blocks walked and inflated (the threaded part) | records decoded and collated
+ * (one thread; SAM: all of feed) | runs copied into the views; any pointer may be NULL */
+int smaltgpu_alnreads_times(const smaltgpu_alnreads *r, double *inflate_s, double *decode_s, double *take_s);
+
 /* ---- split reads (smalt map -p): rmapSingle with RMAPFLG_SPLIT (rmap.c:1716-1728 -> mapSecondary, rmap.c:1435-1505) for a batch ----
  * Every read is mapped; where the best alignment of the read's first segment leaves a stretch of at least a word and a step
  * uncovered, the read is mapped once more with k-mer words from that stretch only (smaltgpu_callctx.seed_range), into the same

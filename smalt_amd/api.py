@@ -84,6 +84,9 @@ class ReadsView(C.Structure):          # smaltgpu_reads_view
                 ("read_off", C.POINTER(C.c_uint64)), ("names", C.POINTER(C.c_char)), ("name_off", C.POINTER(C.c_uint64)), ("consumed", C.c_uint64)]
 
 
+IN_SAM, IN_BAM = 1, 2                  # smaltgpu_alnreads_create (smalt map -F sam | bam)
+
+
 class ReportOpts(C.Structure):         # smaltgpu_report_opts
     _fields_ = [("format", C.c_int32), ("modflags", C.c_uint32), ("outflags", C.c_uint32), ("min_swscor", C.c_int32),
                 ("min_swscor_below_max", C.c_int32), ("min_identity", C.c_double)]
@@ -209,6 +212,12 @@ def lib():
         L.smaltgpu_report_set_reference.argtypes = [C.c_void_p, C.c_void_p]      # the packed host copy (smaltgpu_index_packed_host) for REP_ALIOUT
         L.smaltgpu_report_pair_inserts.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32)]
         L.smaltgpu_report_finish.argtypes = [C.c_void_p, C.POINTER(ReportOpts), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]      # FMT_BAM: the end-of-file block
+        L.smaltgpu_alnreads_create.restype = C.c_void_p                                                                             # reads from SAM / BAM files
+        L.smaltgpu_alnreads_create.argtypes = [C.c_int]
+        L.smaltgpu_alnreads_free.argtypes = [C.c_void_p]
+        L.smaltgpu_alnreads_feed.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.smaltgpu_alnreads_take.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(ReadsView), C.POINTER(ReadsView)]
+        L.smaltgpu_alnreads_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -299,6 +308,40 @@ class InsertHistogram:
     def close(self):
         if self.h:
             lib().smaltgpu_inshist_free(self.h)
+            self.h = None
+
+
+class AlnReads:
+    """Reads from a SAM or BAM file (smaltgpu_alnreads; `smalt map -F sam|bam`): single reads and pairs, collated over the whole
+    input.  feed() takes the next bytes of the file, take() hands out runs of templates of one kind.  Host code; needs no device."""
+
+    def __init__(self, fmt: int):
+        self.h = lib().smaltgpu_alnreads_create(fmt)
+        if not self.h:
+            raise SmaltGpuError(-3, lib().smaltgpu_last_error().decode())
+        self.reads, self.mates = ReadsView(), ReadsView()
+
+    def feed(self, data: bytes, is_last: bool, nthreads: int = 1) -> int:
+        """-> how many of the bytes were used (whole SAM lines, whole BGZF blocks): the next call starts from there"""
+        used = C.c_uint64()
+        _check(lib().smaltgpu_alnreads_feed(self.h, data, len(data), 1 if is_last else 0, nthreads, C.byref(used)))
+        return used.value
+
+    def take(self, max_templates: int = 0):
+        """-> (kind, reads, mates): kind 0 none ready, 1 single reads, 2 pairs; the two ReadsView hold until the next take"""
+        kind = C.c_int()
+        _check(lib().smaltgpu_alnreads_take(self.h, max_templates, C.byref(kind), C.byref(self.reads), C.byref(self.mates)))
+        return kind.value, self.reads, self.mates
+
+    def times(self):
+        """-> seconds spent so far: (BGZF blocks inflated, records decoded and collated, runs copied out)"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().smaltgpu_alnreads_times(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if self.h:
+            lib().smaltgpu_alnreads_free(self.h)
             self.h = None
 
 

@@ -2,6 +2,8 @@
 //   FASTQ/FASTA text --smaltgpu_reads_parse--> batch --smaltgpu_map_batch (GPU)--> raw alignments
 //   --smaltgpu_postprocess--> mapping qualities, order --smaltgpu_report_emit--> CIGAR / SAM text;
 //   two files of mates: --smaltgpu_map_pairs (the rounds of rmapPair on the GPU)--> --smaltgpu_report_emit_pairs--> text;
+//   -F sam|bam (or a file that begins with the BAM magic): one file of single reads and pairs --smaltgpu_alnreads_feed / _take-->
+//   runs of single reads and runs of pairs, each run a block that takes the route of its kind; blocks are written in order;
 //   -a: the report also gets the host copy of the packed reference and prints every mapped alignment in blocks behind its line.
 // The option letters, defaults and derived flags follow the reference's `smalt map` (menu.c:1147-1160 defaults,
 // :1340-1345 -d, :1487-1497 -r; smalt.c:209-245 output formats, :490-503 result flags, :608-615 default -m) so that the
@@ -48,9 +50,16 @@ const char VERSION[] = "0.2";
 void usage() {
   fprintf(stderr,
           "usage: smaltgpu-map [options] <index prefix> <reads.fq|reads.fa>[.gz] [<mates.fq|mates.fa>[.gz]]\n"
+          "       smaltgpu-map [options] -F sam|bam <index prefix> <reads.sam|reads.bam>\n"
           "  -f <fmt>   cigar (default) | ssaha | sam | samsoft | bam, SAM modifiers behind a colon: nohead, clip, x (e.g. sam:nohead,x);\n"
           "             bam: the SAM records in binary (BGZF blocks, deflate level SMALTGPU_BAM_LEVEL=0..9), same modifiers (e.g. bam:x)\n"
           "  -o <file>  output file (default: standard output)\n"
+          "  -F <fmt>   input format: fastq (default: FASTQ or FASTA text, plain or gzip) | sam | bam.  sam, bam: ONE input file that may hold\n"
+          "             single reads and read pairs mixed (unaligned or aligned; secondary and supplementary records are dropped, reads on\n"
+          "             the reverse strand are turned back); mates are found by name anywhere in the file and mapped as pairs with -i -j -l -I,\n"
+          "             everything else as single reads, in the order of the templates.  Without -F a file that begins with the BAM magic is\n"
+          "             read as BAM; SAM needs -F sam.  The table of waiting mates is kept in memory\n"
+          "  -T <dir>   accepted without effect: there are no temporary files (the reference keeps those of its BAM reader there)\n"
           "  -m <int>   minimum Smith-Waterman score (default: word length + step - 1)\n"
           "  -d <int>   report alignments within <int> of the best score; -1: all (default 0: best only)\n"
           "  -r <int>   seed for the random choice among equally good alignments; < 0: such reads are reported unmapped;\n"
@@ -99,6 +108,14 @@ struct Kept {
     names.insert(names.end(), v.names + v.name_off[i], v.names + v.name_off[i + 1]);
     read_off.push_back(bases.size()); name_off.push_back(names.size());
   }
+  void assign(const smaltgpu_reads_view &v) {                                      // a whole view (a run of the SAM / BAM reader)
+    const uint32_t n = v.nreads;
+    bases.assign(v.bases, v.bases + v.read_off[n]);
+    has_qual = v.has_qual && v.quals;
+    if (has_qual) quals.assign(v.quals, v.quals + v.read_off[n]); else quals.clear();
+    names.assign(v.names, v.names + v.name_off[n]);
+    read_off.assign(v.read_off, v.read_off + n + 1); name_off.assign(v.name_off, v.name_off + n + 1);
+  }
   void view(smaltgpu_reads_view *v) const {
     v->nreads = (uint32_t)(read_off.size() - 1); v->has_qual = has_qual && v->nreads ? 1 : 0;
     v->bases = bases.data(); v->quals = v->has_qual ? quals.data() : nullptr; v->read_off = read_off.data();
@@ -111,6 +128,7 @@ struct Block {                                  // one block of reads (or pairs)
   smaltgpu_reads *rs = nullptr, *rs2 = nullptr;
   smaltgpu_reads_view v, v2;                    // v2: the mates
   smaltgpu_pairs *pairs = nullptr;
+  int kind = 1;                                 // 1: single reads, 2: pairs (a run of a SAM / BAM file is of one kind)
   uint32_t maxlen = 0;
   std::vector<uint32_t> hitlen;                 // serial-order mode: per read the longest read (>= k bases) of the input so far
   int state = 0;                                // 0 free, 1 parsed, 2 mapped + post-processed, 3 end of input
@@ -128,7 +146,7 @@ struct Source {
   bool gz = false, gz_end = false;
   z_stream zs;
   std::vector<char> buf; uint64_t boff = 0;                     // inflated text not consumed yet: buf[boff..)
-  void open(const char *path) {
+  void open(const char *path, bool raw = false) {              // raw: the bytes of the file as they are, also when they are gzip members
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) die("cannot open", path);
     struct stat sb;
@@ -137,7 +155,7 @@ struct Source {
     map = maplen ? (const char *)mmap(nullptr, maplen, PROT_READ, MAP_PRIVATE, fd, 0) : "";
     if (maplen && map == (const char *)MAP_FAILED) die("cannot map", path);
     if (maplen) (void)madvise((void *)map, maplen, MADV_SEQUENTIAL);
-    gz = maplen >= 2 && (unsigned char)map[0] == 0x1f && (unsigned char)map[1] == 0x8b;
+    gz = !raw && maplen >= 2 && (unsigned char)map[0] == 0x1f && (unsigned char)map[1] == 0x8b;
     if (gz) {
       memset(&zs, 0, sizeof(zs));
       if (inflateInit2(&zs, 15 + 32) != Z_OK) die("zlib");          // + 32: gzip or zlib header
@@ -230,7 +248,7 @@ int index_main(int argc, char **argv) {
 int main(int argc, char **argv) {
   if (argc > 1 && !strcmp(argv[1], "index")) return index_main(argc, argv);
   const bool sampling = argc > 1 && !strcmp(argv[1], "sample");
-  const char *fmt = sampling ? "sam:nohead" : "cigar", *oufil = nullptr, *scorespec = nullptr, *histfil = nullptr;   // sample prints SAM lines without a header
+  const char *fmt = sampling ? "sam:nohead" : "cigar", *oufil = nullptr, *scorespec = nullptr, *histfil = nullptr, *infmt = nullptr;   // sample prints SAM lines without a header
   int m = -1, d = 0, seed = 0, q = 0, nthreads = 0, ins_max = 500, ins_min = 0, lib = SMALTGPU_LIB_PE, every = 100;    // -u: MENU_DEFAULTS_READSKIP (menu.c:618)
   std::vector<int> devices;
   bool d_given = false, randrepeat = true, exhaustive = false, split = false, weighted = false, aliout = false;
@@ -245,10 +263,7 @@ int main(int argc, char **argv) {
     if (o == 'a' && !argv[a][2] && !sampling) { aliout = true; continue; }         // (nor -a)
     if (o == 'O' && !argv[a][2] && !sampling) continue;                            // output in input order: always the case here
     if (sampling && !strchr("mnoquBg", o)) usage();
-    if (argv[a][2] || !strchr("fomdrycqnBgijlSIu", o) || (o == 'u' && !sampling)) {
-      if (strchr("TF", o) && !argv[a][2]) die("option not supported by this program (use the bound `smalt map`, INTEGRATION.md)", argv[a]);
-      usage();
-    }
+    if (argv[a][2] || !strchr("fomdrycqnBgijlSIuFT", o) || (o == 'u' && !sampling)) usage();
     if (a + 1 >= argc) usage();
     const char *val = argv[++a];
     switch (o) {
@@ -266,6 +281,8 @@ int main(int argc, char **argv) {
       case 'l': lib = !strcmp(val, "pe") ? SMALTGPU_LIB_PE : !strcmp(val, "mp") ? SMALTGPU_LIB_MP : !strcmp(val, "pp") ? SMALTGPU_LIB_PP : 0; if (!lib) die("-l: pe, mp or pp"); break;
       case 'S': scorespec = val; break;
       case 'I': histfil = val; break;
+      case 'F': infmt = val; break;
+      case 'T': break;                                                                  // a place for temporary files: there are none
       case 'u': every = atoi(val); break;
       case 'B': batch = atol(val); if (batch < 1 || batch > (1L << 20)) die("-B out of range (1 .. 1048576)"); break;
       case 'g': for (const char *c = val; *c;) { devices.push_back(atoi(c)); while (*c && *c != ',') c++; if (*c) c++; } break;
@@ -275,7 +292,18 @@ int main(int argc, char **argv) {
   if (argc - a != 2 && argc - a != 3) usage();
   const char *prefix = argv[a], *readfil = argv[a + 1], *matefil = argc - a == 3 ? argv[a + 2] : nullptr;
   const bool paired = matefil != nullptr;
-  if (paired && ins_min > ins_max) die("-j above -i");
+  int alnfmt = 0;                                                                        // SMALTGPU_IN_*: reads from a SAM / BAM file
+  if (infmt) {                                                                           // -F (menu.c:1368-1378)
+    if (!strcmp(infmt, "sam")) alnfmt = SMALTGPU_IN_SAM;
+    else if (!strcmp(infmt, "bam")) alnfmt = SMALTGPU_IN_BAM;
+    else if (strcmp(infmt, "fastq")) die("-F: input format not supported here (fastq, sam, bam)", infmt);
+    if (alnfmt && matefil) die("-F sam|bam takes exactly one input file (it holds the mates too)", matefil);
+  }
+  // SMALTGPU_SERIAL_ORDER=1 (single reads): the output of a serial `smalt map -n 0` also where it depends on the order of reads of
+  // different lengths (the capacity of the reference's hit list follows the longest read so far)
+  const bool serial_order = getenv("SMALTGPU_SERIAL_ORDER") && atoi(getenv("SMALTGPU_SERIAL_ORDER")) != 0;
+  if (serial_order && alnfmt) die("SMALTGPU_SERIAL_ORDER=1 does not go with -F sam|bam: runs of pairs have no serial order of hit lists");
+  if ((paired || alnfmt) && ins_min > ins_max) die("-j above -i");
   if (!strncmp(fmt, "bam", 3) && (!fmt[3] || fmt[3] == ':')) {                             // binary output: nothing else may go into it
     if (aliout) die("-a does not go with -f bam: a BAM file has no place for alignment blocks");
     if (histfil && !oufil) die("-I with -f bam needs -o <file>: the two histogram prints go to standard output");
@@ -354,8 +382,18 @@ int main(int argc, char **argv) {
     if (count[0] != count[1]) die("the two read files hold different numbers of reads");
     interval = (uint32_t)smaltgpu_sample_interval(count[0], every);
   }
-  src.open(readfil);
+  src.open(readfil, alnfmt == SMALTGPU_IN_BAM);
+  if (!infmt && !paired && !sampling && src.gz) {                                        // the reference guesses too (infmt.c:134-148): a BAM file by its magic
+    uint64_t got = 0; bool last = false;
+    const char *head = src.window(4, &got, &last);
+    const bool bam = got >= 4 && !memcmp(head, "BAM\1", 4);
+    src.close();
+    if (bam) alnfmt = SMALTGPU_IN_BAM;
+    src.open(readfil, bam);
+  }
+  if (serial_order && alnfmt) die("SMALTGPU_SERIAL_ORDER=1 does not go with BAM input: runs of pairs have no serial order of hit lists");
   if (paired) src2.open(matefil);
+  if (alnfmt && ins_min > ins_max) die("-j above -i");
   FILE *ou = oufil ? fopen(oufil, "w") : stdout;
   if (!ou) die("cannot write", oufil);
   static char oubuf[1 << 22];
@@ -435,7 +473,9 @@ int main(int argc, char **argv) {
   if (per_dev * ndev > MAXWORK) per_dev = MAXWORK / ndev;
   const int NWORK = per_dev * ndev, NBLK = NWORK + 2;
   std::vector<Block> blk((size_t)NBLK);
-  for (Block &b : blk) { b.rs = smaltgpu_reads_create(); if (paired) { b.rs2 = smaltgpu_reads_create(); b.pairs = smaltgpu_pairs_create(); } }
+  for (Block &b : blk) { b.rs = smaltgpu_reads_create(); b.kind = paired ? 2 : 1; if (paired) { b.rs2 = smaltgpu_reads_create(); b.pairs = smaltgpu_pairs_create(); } }
+  smaltgpu_alnreads *aln = alnfmt ? smaltgpu_alnreads_create(alnfmt) : nullptr;            // owned by the parser thread until it is joined
+  if (alnfmt && !aln) die("input", smaltgpu_last_error());
   // a failing call's text, never empty (the block must not pass for mapped when a call failed without a message)
   auto why = [](const char *what) { const char *e = smaltgpu_last_error(); return std::string(e && *e ? e : what); };
   std::mutex mu;
@@ -446,13 +486,11 @@ int main(int argc, char **argv) {
   double t_parse = 0, t_create[MAXWORK] = {0}, t_map[MAXWORK] = {0}, t_post[MAXWORK] = {0};          // seconds per stage (SMALTGPU_MAP_VERBOSE)
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 
-  // SMALTGPU_SERIAL_ORDER=1 (single reads): the output of a serial `smalt map -n 0` also where it depends on the order of reads of
-  // different lengths (the capacity of the reference's hit list follows the longest read so far)
-  const bool serial_order = getenv("SMALTGPU_SERIAL_ORDER") && atoi(getenv("SMALTGPU_SERIAL_ORDER")) != 0;
   uint32_t longest_so_far = 0;
   std::thread parser([&] {
     double bytes_per_read = 0.0;
-    uint64_t pairs_seen = 0;
+    uint64_t pairs_seen = 0, aln_bytes = 0, aln_templates = 0;
+    bool aln_ended = false;
     for (uint64_t k = 0;; k++) {
       Block &b = blk[k % NBLK];
       { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return failed || k < n_written + NBLK; }); if (failed) return; }
@@ -473,7 +511,30 @@ int main(int argc, char **argv) {
           w *= 4;                                          // not enough complete records in the window
         }
       };
-      if (sampling) {
+      if (aln) {
+        // the next run of the file: single reads or pairs, at most a batch of them; the reader is fed until it has one
+        int kind = 0;
+        uint64_t w = bytes_per_read > 0 ? (uint64_t)(bytes_per_read * (double)batch * 1.05) + 65536 : (1u << 20);
+        for (;;) {
+          smaltgpu_reads_view tv, tv2;
+          if (smaltgpu_alnreads_take(aln, (uint32_t)batch, &kind, &tv, &tv2)) { std::lock_guard<std::mutex> lk(mu); b.err = why("cannot read the input"); failed = true; cv.notify_all(); return; }
+          if (kind) {                                      // the views hold until the next take: the block keeps its own copy
+            b.kind = kind;
+            b.kept[0].assign(tv); b.kept[0].view(&b.v);
+            if (kind == 2) { b.kept[1].assign(tv2); b.kept[1].view(&b.v2); if (!b.pairs) b.pairs = smaltgpu_pairs_create(); }
+            break;
+          }
+          if (aln_ended) { b.v.nreads = 0; break; }
+          uint64_t got = 0, used = 0; bool last = false;
+          const char *bytes = src.window(w, &got, &last);
+          if (smaltgpu_alnreads_feed(aln, bytes, got, last ? 1 : 0, nthreads, &used)) { std::lock_guard<std::mutex> lk(mu); b.err = why("cannot read the input"); failed = true; cv.notify_all(); return; }
+          src.consume(used);
+          aln_bytes += used;
+          if (last) aln_ended = true;
+          else if (!used) w *= 4;                          // not one whole line or block in the window
+        }
+        if (b.v.nreads) { aln_templates += b.v.nreads; bytes_per_read = (double)aln_bytes / (double)aln_templates; }
+      } else if (sampling) {
         // stretches of the input are parsed until a block of sampled pairs is full: pair i is kept when i % interval == 0 (smalt.c:809-818)
         b.kept[0].clear(); b.kept[1].clear();
         for (;;) {
@@ -492,7 +553,7 @@ int main(int argc, char **argv) {
         }
         b.kept[0].view(&b.v); b.kept[1].view(&b.v2);
       } else if (!parse_from(src, b.rs, &b.v, (uint32_t)batch, false)) return;
-      if (sampling) {                                      // both files are parsed above
+      if (sampling || aln) {                               // both sides are there
       } else if (paired && b.v.nreads) {
         if (!parse_from(src2, b.rs2, &b.v2, b.v.nreads, true)) return;
         if (b.v2.nreads != b.v.nreads) { std::lock_guard<std::mutex> lk(mu); b.err = "the two read files hold different numbers of reads"; failed = true; cv.notify_all(); return; }
@@ -503,14 +564,14 @@ int main(int argc, char **argv) {
       }
       if (!b.v.nreads) { std::lock_guard<std::mutex> lk(mu); n_blocks_total = k; input_done = true; cv.notify_all(); return; }
       t_parse += now() - tp0;
-      if (!sampling) {
+      if (!sampling && !aln) {
         bytes_per_read = (double)b.v.consumed / (double)b.v.nreads;
         src.consume(b.v.consumed);
         if (paired) src2.consume(b.v2.consumed);
       }
       b.maxlen = 1;
       for (uint32_t i = 0; i < b.v.nreads; i++) { const uint32_t l = (uint32_t)(b.v.read_off[i + 1] - b.v.read_off[i]); if (l > b.maxlen) b.maxlen = l; }
-      if (paired) for (uint32_t i = 0; i < b.v2.nreads; i++) { const uint32_t l = (uint32_t)(b.v2.read_off[i + 1] - b.v2.read_off[i]); if (l > b.maxlen) b.maxlen = l; }
+      if (b.kind == 2) for (uint32_t i = 0; i < b.v2.nreads; i++) { const uint32_t l = (uint32_t)(b.v2.read_off[i + 1] - b.v2.read_off[i]); if (l > b.maxlen) b.maxlen = l; }
       b.hitlen.clear();
       if (serial_order && !paired) {                       // the reference's one hit list only grows (hashhit.c:1280): smaltgpu_callctx.hitlist_len
         b.hitlen.resize(b.v.nreads);
@@ -551,7 +612,8 @@ int main(int argc, char **argv) {
         else { W.cap_reads = cr; W.cap_len = cl > W.cap_len ? cl : W.cap_len; if (!paired) smaltgpu_mapper_set_host_threads(W.mp, nthreads > 4 ? nthreads / 4 : 1); }
       }
       t1 = now(); t_create[w] += t1 - t0; t0 = t1;
-      if (err.empty() && paired) {
+      if (err.empty() && b.kind == 1 && aln) smaltgpu_mapper_set_host_threads(W.mp, nthreads > 4 ? nthreads / 4 : 1);      // (a run of pairs leaves it at 1)
+      if (err.empty() && b.kind == 2) {
         // the rounds of rmapPair for the block; the results rest in the block, the mapper is free for the next one
         const bool q2 = b.v.has_qual && b.v2.has_qual;
         if (smaltgpu_map_pairs(W.mp, b.v.bases, q2 ? b.v.quals : nullptr, b.v.read_off, b.v2.bases, q2 ? b.v2.quals : nullptr, b.v2.read_off, b.v.nreads, &par, &po, b.pairs))
@@ -573,7 +635,7 @@ int main(int argc, char **argv) {
                                                 nthreads > 2 ? nthreads / 2 : 1, &b.post)) err = why("post-processing failed");
         t_post[w] += now() - t0;
       }
-      { std::lock_guard<std::mutex> lk(mu); b.worker = w; if (paired) W.busy = false; if (!err.empty()) { b.err = err; failed = true; } b.state = 2; cv.notify_all(); }
+      { std::lock_guard<std::mutex> lk(mu); b.worker = w; if (b.kind == 2) W.busy = false; if (!err.empty()) { b.err = err; failed = true; } b.state = 2; cv.notify_all(); }
     }
   };
   std::vector<std::thread> workers;
@@ -594,7 +656,7 @@ int main(int argc, char **argv) {
     }
     const char *txt; uint64_t tl;
     t1 = now(); t_wait += t1 - t0; t0 = t1;
-    if (paired ? smaltgpu_report_emit_pairs(rep, b.pairs, &b.v, &b.v2, seqnames, nseq, &ro, &po, nthreads, &txt, &tl)
+    if (b.kind == 2 ? smaltgpu_report_emit_pairs(rep, b.pairs, &b.v, &b.v2, seqnames, nseq, &ro, &po, nthreads, &txt, &tl)
                : smaltgpu_report_emit(rep, &b.post, split ? nullptr : &b.raw, &b.v, seqnames, nseq, &ro, nthreads, &txt, &tl)) failure = why("formatting the report failed");
     t1 = now(); t_emit += t1 - t0; t0 = t1;
     if (failure.empty() && tl && fwrite(txt, 1, tl, ou) != tl) failure = "write error";
@@ -605,7 +667,7 @@ int main(int argc, char **argv) {
       else for (uint32_t i = 0; i < np; i++) if (known[i]) sample.push_back(isz[i]);
     }
     nreads_total += b.v.nreads;
-    { std::lock_guard<std::mutex> lk(mu); b.state = 0; if (!paired) wk[b.worker].busy = false; n_written = k + 1; if (!failure.empty()) failed = true; cv.notify_all(); }
+    { std::lock_guard<std::mutex> lk(mu); b.state = 0; if (b.kind != 2) wk[b.worker].busy = false; n_written = k + 1; if (!failure.empty()) failed = true; cv.notify_all(); }
     if (!failure.empty()) break;
   }
   { std::lock_guard<std::mutex> lk(mu); if (!failure.empty()) failed = true; cv.notify_all(); }
@@ -614,6 +676,9 @@ int main(int argc, char **argv) {
   if (failed && failure.empty()) for (Block &x : blk) if (!x.err.empty()) failure = x.err;
   for (Worker &W : wk) { if (W.mp) smaltgpu_mapper_free(W.mp); if (W.post) smaltgpu_post_free(W.post); }
   for (Block &b : blk) { smaltgpu_reads_free(b.rs); if (b.rs2) smaltgpu_reads_free(b.rs2); if (b.pairs) smaltgpu_pairs_free(b.pairs); }
+  double aln_s[3] = {0, 0, 0};
+  if (aln) smaltgpu_alnreads_times(aln, &aln_s[0], &aln_s[1], &aln_s[2]);
+  smaltgpu_alnreads_free(aln);
   if (sampling && !failed && failure.empty()) {             // outputHisto (smalt.c:1288-1310)
     smaltgpu_inshist *sh = nullptr;
     std::string tail;
@@ -648,6 +713,8 @@ int main(int argc, char **argv) {
     for (int w = 0; w < NWORK; w++) { tc += t_create[w]; tm_ += t_map[w]; tp += t_post[w]; }
     fprintf(stderr, "smaltgpu-map: stages [s]: parse %.3f | %d workers on %d device(s), mean per worker: mapper set-up %.3f  map %.3f  post %.3f | wait %.3f emit %.3f write %.3f\n",
             t_parse, NWORK, ndev, tc / NWORK, tm_ / NWORK, tp / NWORK, t_wait, t_emit, t_write);
+    if (alnfmt) fprintf(stderr, "smaltgpu-map: of parse [s]: inflate %.3f  decode and collate %.3f  runs copied out %.3f (the rest: copies into the blocks, page faults of the input)\n",
+                        aln_s[0], aln_s[1], aln_s[2]);
   }
   return 0;
 }
