@@ -559,9 +559,55 @@ long smaltgpu_dump_read(smaltgpu_mapper *m, uint32_t i, const char *name, char *
 /* Stand-alone kernel entry points used by the parity tests (host pointers in, host out). */
 /* K2a (swsimd.c:868, un-banded score pass) over explicit 3-bit code arrays.  packed16 = 1: the kernel that scores two
  * tasks per lane group in 16-bit halves (a task whose query holds non-ACGT codes reports -2: the mapper routes those
- * to the 32-bit kernel); packed16 = 0: the 32-bit kernel.  -1: task too long for the register tiling. */
+ * to the 32-bit kernel); packed16 = 0: the 32-bit kernel.  A batch with a read above 512 bases or a window above 1016
+ * goes to the strip kernels: packed16 = 0 to the 32-bit one, packed16 = 1 to the packed one (tasks 2t and 2t+1 share a
+ * wave; its max3 form where the longest read's best score + 512 stays below 0x7C00, else its plain form;
+ * SMALTGPU_EARG if the penalties or match x longest read >= 60000 rule the 16-bit halves out).  Score -1: window above
+ * the register tiling or, in the strip kernels, above the mapper's window capacity. */
 int smaltgpu_sw_full_batch(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
                            const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, int32_t *scores, int packed16);
+
+/* K2b (alignment.c:1029, banded score pass) over explicit 3-bit code arrays: band[4t..4t+3] = {band_l, band_r, qs, qe} of
+ * task t, the band set up over the whole window as the mapper does.  form 0: the wave kernel's pass (one wave per task),
+ * form 1: the one-lane pass.  The windows are packed back to back in the index's layout (10 bases per word), so they start
+ * at every phase of a word.  status[t] = 1 where the band is refused (the mapper drops such a candidate), else 0. */
+int smaltgpu_sw_band_batch(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
+                           const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, const int32_t *band, int form,
+                           int32_t *scores, int32_t *status);
+
+/* K3, one node of the recursion (alignment.c:1300): band set-up over the window rows [s_left, s_right], the band pass in ONE
+ * named form, the traceback the mapper pairs with that form, and the forward DiffStr.  A task outside the form's
+ * precondition fails the whole call with SMALTGPU_EARG; there is no fall-back to another form. */
+enum {
+  SMALTGPU_BAND_ROWS = 0,      /* 1..64 diagonals, gap_init >= gap_ext >= 0 in absolute value; lds = 1: read and window (and the
+                                  directions, if they fit) staged in LDS */
+  SMALTGPU_BAND_ANTIDIAG = 1,  /* 1..64 diagonals */
+  SMALTGPU_BAND_WAVE2 = 2, SMALTGPU_BAND_WAVE4 = 3, SMALTGPU_BAND_WAVE7 = 4, SMALTGPU_BAND_WAVE12 = 5,  /* (r_edge - l_edge) / 128 + 1 <= N */
+  SMALTGPU_BAND_STRIP8 = 6,    /* 256 <= diagonals < 2048 */
+  SMALTGPU_BAND_STRIP16 = 7,   /* diagonals >= 2048 */
+  SMALTGPU_BAND_SCALAR = 8,    /* any band, one lane */
+  SMALTGPU_BAND_NFORMS = 9
+};
+enum { SMALTGPU_NODE_ALIGNED = 0, SMALTGPU_NODE_REFUSED = 1 /* band refused: no node */, SMALTGPU_NODE_BELOW = 2 /* maximum below minscore */ };
+typedef struct smaltgpu_band_node {
+  int32_t status;              /* SMALTGPU_NODE_* or SMALTGPU_ESCORE / SMALTGPU_EINTERNAL / SMALTGPU_ECAP */
+  int32_t score, max_i, max_j; /* maximum of the pass and its first cell in row-major order (window row, read column) */
+  int32_t qs, rs;              /* where the traceback ends */
+  int32_t dlen;                /* forward DiffStr with its terminator: dstr[stroffs .. stroffs + dlen) */
+  uint32_t stroffs;
+} smaltgpu_band_node;
+/* band as above; iv[2t..2t+1] = {s_left, s_right}; tw = 1: directions of the anti-diagonal and wave forms in the
+ * anti-diagonal-major layout the mapper uses for a direction matrix in HBM, tw = 0: row-major (other forms ignore it);
+ * dstr: room for the sum over the tasks of (read length + window length + 16) bytes. */
+int smaltgpu_band_align_nodes(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
+                              const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, const int32_t *band, const int32_t *iv,
+                              int minscore, int form, int lds, int tw, smaltgpu_band_node *out, uint8_t *dstr);
+/* Host only: the band of such a node as the kernels see it.  geo[0..12] = band_width, l_edge_orig, r_edge_orig, l_edge, r_edge,
+ * s_left_orig, s_left, s_len, s_totlen, q_left_orig, q_left, q_len, q_totlen; geo[13] = the form the mapper's K3 kernel for
+ * long reads picks for it (SMALTGPU_BAND_*; an HBM direction matrix with room for any layout assumed).  Returns 0, or 1 if
+ * the band is refused (geo is then undefined). */
+int smaltgpu_band_geometry(int band_l, int band_r, int qs, int qe, int qlen, int s_left, int s_right, int wlen, int gap_init,
+                           int gap_ext, int32_t *geo);
 
 /* Which sweeps the packed K2a kernel runs in its row-frame form: the largest number of sweep steps (window
  * rows + G - 1) for these penalties (gap scores negative, as in smaltgpu_params) and a tiling of ncols = G * C read

@@ -121,6 +121,38 @@ class BatchOut(C.Structure):
                 ("diffstr", C.POINTER(C.c_uint8)), ("stat", C.POINTER(ReadStat))]
 
 
+class BandNode(C.Structure):           # smaltgpu_band_node
+    _fields_ = [("status", C.c_int32), ("score", C.c_int32), ("max_i", C.c_int32), ("max_j", C.c_int32), ("qs", C.c_int32),
+                ("rs", C.c_int32), ("dlen", C.c_int32), ("stroffs", C.c_uint32)]
+
+
+# SMALTGPU_BAND_*: the forms of the K3 band pass (smaltgpu_band_align_nodes)
+BAND_ROWS, BAND_ANTIDIAG, BAND_WAVE2, BAND_WAVE4, BAND_WAVE7, BAND_WAVE12, BAND_STRIP8, BAND_STRIP16, BAND_SCALAR = range(9)
+NODE_ALIGNED, NODE_REFUSED, NODE_BELOW = 0, 1, 2
+ESCORE, EINTERNAL = -8, -6
+BAND_GEO_FIELDS = ("band_width", "l_edge_orig", "r_edge_orig", "l_edge", "r_edge", "s_left_orig", "s_left", "s_len", "s_totlen",
+                   "q_left_orig", "q_left", "q_len", "q_totlen", "form")
+
+
+def band_geometry(band_l, band_r, qs, qe, qlen, s_left, s_right, wlen, gap_init, gap_ext):
+    """Host only: the band of a K3 node as the kernels set it up and the form the mapper picks for it; None if refused."""
+    geo = (C.c_int32 * 14)()
+    rv = lib().smaltgpu_band_geometry(band_l, band_r, qs, qe, qlen, s_left, s_right, wlen, gap_init, gap_ext, geo)
+    if rv < 0:
+        _check(rv)
+    return None if rv else dict(zip(BAND_GEO_FIELDS, list(geo)))
+
+
+def _offsets(seqs):
+    off = (C.c_uint32 * (len(seqs) + 1))()
+    a = 0
+    for i, s in enumerate(seqs):
+        off[i] = a
+        a += len(s)
+    off[len(seqs)] = a
+    return off
+
+
 _lib = None
 
 
@@ -196,6 +228,12 @@ def lib():
         L.smaltgpu_dump_read.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_size_t]
         L.smaltgpu_sw_full_batch.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p,
                                              C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Params), C.POINTER(C.c_int32), C.c_int]
+        L.smaltgpu_sw_band_batch.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32,
+                                             C.POINTER(Params), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.smaltgpu_band_align_nodes.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32,
+                                                C.POINTER(Params), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(BandNode), C.c_char_p]
+        L.smaltgpu_band_geometry.argtypes = [C.c_int] * 10 + [C.POINTER(C.c_int32)]
         L.smaltgpu_sw_rowframe_max_steps.argtypes = [C.c_int] * 5
         L.smaltgpu_sw_pairframe_max_steps.argtypes = [C.c_int] * 5
         L.smaltgpu_rank_sort_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -627,6 +665,31 @@ class Mapper:
         sc = (C.c_int32 * n)()
         _check(lib().smaltgpu_sw_full_batch(self.h, b"".join(queries), qo, b"".join(windows), ro, n, C.byref(params), sc, int(packed16)))
         return list(sc)
+
+    def sw_band_batch(self, queries: Sequence[bytes], windows: Sequence[bytes], params: Params, bands, form: int = 0):
+        """Stand-alone K2b; bands: (band_l, band_r, qs, qe) per task; form 0: wave kernel, 1: one lane per task.
+        Returns (scores, status) with status 1 where the band is refused."""
+        n = len(queries)
+        bd = (C.c_int32 * (4 * n + 4))(*[int(v) for b in bands for v in b])
+        sc, st = (C.c_int32 * (n + 1))(), (C.c_int32 * (n + 1))()
+        _check(lib().smaltgpu_sw_band_batch(self.h, b"".join(queries), _offsets(queries), b"".join(windows), _offsets(windows), n,
+                                            C.byref(params), bd, form, sc, st))
+        return list(sc)[:n], list(st)[:n]
+
+    def band_align_nodes(self, queries: Sequence[bytes], windows: Sequence[bytes], params: Params, bands, ivs, minscore: int, form: int,
+                         lds: bool = False, tw: bool = False):
+        """Stand-alone K3 nodes in one form of the band pass; bands: (band_l, band_r, qs, qe), ivs: (s_left, s_right) per task.
+        Returns per task a dict(status, score, max_i, max_j, qs, rs, diffstr)."""
+        n = len(queries)
+        bd = (C.c_int32 * (4 * n + 4))(*[int(v) for b in bands for v in b])
+        iv = (C.c_int32 * (2 * n + 2))(*[int(v) for b in ivs for v in b])
+        out = (BandNode * (n + 1))()
+        ds = C.create_string_buffer(sum(len(q) + len(w) + 16 for q, w in zip(queries, windows)) + 16)
+        _check(lib().smaltgpu_band_align_nodes(self.h, b"".join(queries), _offsets(queries), b"".join(windows), _offsets(windows), n,
+                                               C.byref(params), bd, iv, minscore, form, int(lds), int(tw), out, ds))
+        raw = ds.raw
+        return [dict(status=o.status, score=o.score, max_i=o.max_i, max_j=o.max_j, qs=o.qs, rs=o.rs,
+                     diffstr=raw[o.stroffs:o.stroffs + o.dlen]) for o in out[:n]]
 
     def rank_sort_batch(self, arrays, nneed: int = -1, in_lds: bool = True):
         """Stand-alone candidate ranking sort: list of uint32 numpy arrays -> list of (keys, permutation)."""

@@ -1307,12 +1307,145 @@ extern "C" int smaltgpu_sw_full_batch(smaltgpu_mapper *m, const uint8_t *qcodes,
     int lr;
     if (!packed16 && (qmaxlen > 512 || rmaxlen > (uint32_t)SW_FULL_WMAX))     // beyond the register tiling: the strip kernel (windows up to the mapper's capacity)
       lr = launch_sw_strip_raw(m->stream, dq, dqo, dr, dro, ntask, to_par(par), dsc, m->strip_bnd, m->strip_win, m->wincap, m->strip_grid);
+    else if (packed16 && (qmaxlen > 512 || rmaxlen > (uint32_t)SW_FULL_WMAX))                         // ... and its packed form, two tasks per wave
+      lr = launch_sw_strip16_raw(m->stream, dq, dqo, dr, dro, ntask, to_par(par), dsc, m->strip_bnd, m->strip_win, m->wincap, m->strip_grid, qmaxlen);
     else lr = launch_sw_full_raw(m->stream, dq, dqo, dr, dro, ntask, to_par(par), dsc, qmaxlen, packed16);
     if (lr) rv = fail(SMALTGPU_EARG, lr == -2 ? "scores do not fit the packed 16-bit kernel" : "query longer than the register-tiled kernel supports");
     else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
     else (void)hipMemcpy(scores, dsc, (size_t)ntask * 4, hipMemcpyDeviceToHost);
   }
   (void)hipFree(dq); (void)hipFree(dr); (void)hipFree(dqo); (void)hipFree(dro); (void)hipFree(dsc);
+  return rv;
+}
+
+extern "C" int smaltgpu_sw_band_batch(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
+                                       const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, const int32_t *band, int form,
+                                       int32_t *scores, int32_t *status) {
+  if (!m || !qcodes || !q_off || !rcodes || !r_off || !par || !band || !scores || !status) return fail(SMALTGPU_EARG, "null argument");
+  if (form != 0 && form != 1) return fail(SMALTGPU_EARG, "unknown form");
+  uint32_t qmaxlen = 0, rmaxlen = 0;
+  for (uint32_t t = 0; t < ntask; t++) {
+    const uint32_t ql = q_off[t + 1] - q_off[t], wl = r_off[t + 1] - r_off[t];
+    if (q_off[t + 1] <= q_off[t] || r_off[t + 1] <= r_off[t]) return fail(SMALTGPU_EARG, "empty read or window");
+    if (form == 0 && wl > m->wincap) return fail(SMALTGPU_EARG, "window above the mapper's capacity");
+    if (ql > qmaxlen) qmaxlen = ql;
+    if (wl > rmaxlen) rmaxlen = wl;
+    Band bd;
+    status[t] = band_init(bd, band[4 * t], band[4 * t + 1], band[4 * t + 2], band[4 * t + 3], (int)ql, 0, (int)wl - 1, (int)wl) ? 1 : 0;
+  }
+  // the windows back to back in the index's layout: 10 codes per word, the first in bits 29..27
+  const size_t nbase = r_off[ntask];
+  std::vector<uint32_t> packed(nbase / 10 + 2, 0u);
+  for (size_t o = 0; o < nbase; o++) packed[o / 10] |= (uint32_t)(rcodes[o] & 7u) << (3 * (9 - (uint32_t)(o % 10)));
+  HIPCHK(hipSetDevice(m->device));
+  uint8_t *dq = nullptr; uint32_t *dp = nullptr, *dqo = nullptr, *dro = nullptr; int32_t *dsc = nullptr, *dbd = nullptr; int *drows = nullptr;
+  const uint32_t rowlen = qmaxlen + rmaxlen + 2;      // band_fast_scalar looks one row past a band that has left the read
+  const size_t nrows = form == 1 ? (size_t)((ntask + 63) / 64) * 64 * 2 * rowlen : 1;
+  int rv = 0;
+  if (dalloc(&dq, q_off[ntask] + 16) || dalloc(&dp, packed.size()) || dalloc(&dqo, (size_t)ntask + 1) || dalloc(&dro, (size_t)ntask + 1) ||
+      dalloc(&dsc, (size_t)ntask + 1) || dalloc(&dbd, 4 * (size_t)ntask + 4) || dalloc(&drows, nrows)) rv = SMALTGPU_ENOMEM;
+  if (!rv) {
+    (void)hipMemcpy(dq, qcodes, q_off[ntask], hipMemcpyHostToDevice);
+    (void)hipMemcpy(dp, packed.data(), packed.size() * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dqo, q_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dro, r_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dbd, band, (size_t)ntask * 16, hipMemcpyHostToDevice);
+    (void)hipMemset(drows, 0, nrows * sizeof(int));
+    const int lr = form == 0 ? launch_sw_band_raw(m->stream, dq, dqo, dp, dro, ntask, to_par(par), dbd, dsc, m->strip_bnd, m->strip_win, m->wincap, m->strip_grid)
+                             : launch_sw_band_scalar_raw(m->stream, dq, dqo, dp, dro, ntask, to_par(par), dbd, dsc, drows, rowlen);
+    if (lr) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
+    else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
+    else (void)hipMemcpy(scores, dsc, (size_t)ntask * 4, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dq); (void)hipFree(dp); (void)hipFree(dqo); (void)hipFree(dro); (void)hipFree(dsc); (void)hipFree(dbd); (void)hipFree(drows);
+  return rv;
+}
+
+static_assert(sizeof(smaltgpu_band_node) == sizeof(BandNodeOut), "smaltgpu_band_node is BandNodeOut");
+static_assert((int)SMALTGPU_BAND_NFORMS == (int)BF_NFORMS && (int)SMALTGPU_BAND_SCALAR == (int)BF_SCALAR && (int)SMALTGPU_BAND_STRIP8 == (int)BF_STRIP8, "form numbers");
+
+extern "C" int smaltgpu_band_geometry(int band_l, int band_r, int qs, int qe, int qlen, int s_left, int s_right, int wlen, int gap_init,
+                                       int gap_ext, int32_t *geo) {
+  if (!geo || qlen < 1 || wlen < 1) return fail(SMALTGPU_EARG, "bad argument");
+  Band b;
+  if (band_init(b, band_l, band_r, qs, qe, qlen, s_left, s_right, wlen)) return 1;
+  const int32_t v[14] = {b.band_width, b.l_edge_orig, b.r_edge_orig, b.l_edge, b.r_edge, b.s_left_orig, b.s_left, b.s_len, b.s_totlen,
+                         b.q_left_orig, b.q_left, b.q_len, b.q_totlen, band_form_production(b, -gap_init, -gap_ext)};
+  memcpy(geo, v, sizeof(v));
+  return 0;
+}
+
+extern "C" int smaltgpu_band_align_nodes(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
+                                          const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, const int32_t *band, const int32_t *iv,
+                                          int minscore, int form, int lds, int tw, smaltgpu_band_node *out, uint8_t *dstr) {
+  if (!m || !qcodes || !q_off || !rcodes || !r_off || !par || !band || !iv || !out || !dstr) return fail(SMALTGPU_EARG, "null argument");
+  if (form < 0 || form >= (int)BF_NFORMS || (lds && form != (int)BF_ROWS)) return fail(SMALTGPU_EARG, "unknown form");
+  const MapPar p = to_par(par);
+  const int gi = -p.gap_init, ge = -p.gap_ext;
+  if (form == (int)BF_ROWS && !(gi >= ge && ge >= 0)) return fail(SMALTGPU_EARG, "the row form needs gap_init >= gap_ext >= 0");
+  // per task: the form's precondition on the band the kernel will set up, and the room its directions take
+  std::vector<uint64_t> dir_off((size_t)ntask + 1, 0);
+  std::vector<uint32_t> dstr_off((size_t)ntask + 1, 0);
+  uint32_t qmaxlen = 0, rmaxlen = 0;
+  for (uint32_t t = 0; t < ntask; t++) {
+    if (q_off[t + 1] <= q_off[t] || r_off[t + 1] <= r_off[t]) return fail(SMALTGPU_EARG, "empty read or window");
+    const uint32_t ql = q_off[t + 1] - q_off[t], wl = r_off[t + 1] - r_off[t];
+    if (ql > (1u << 20) || wl > (1u << 20)) return fail(SMALTGPU_EARG, "task too long");
+    if (lds && (ql > NODE_LDS_CODES || wl > NODE_LDS_CODES)) return fail(SMALTGPU_EARG, "read or window too long for the LDS stage");
+    if (ql > qmaxlen) qmaxlen = ql;
+    if (wl > rmaxlen) rmaxlen = wl;
+    Band b;
+    uint64_t need = 16;
+    if (!band_init(b, band[4 * t], band[4 * t + 1], band[4 * t + 2], band[4 * t + 3], (int)ql, iv[2 * t], iv[2 * t + 1], (int)wl) &&
+        b.s_left < b.s_len && b.band_width >= 0) {
+      if (!band_form_ok(form, b, gi, ge)) return fail(SMALTGPU_EARG, "a task's band is outside the form's precondition");
+      need = band_dir_bytes(form, b, tw != 0) + 2 * (uint64_t)wl + 256;
+    }
+    dir_off[t + 1] = dir_off[t] + ((need + 15) & ~(uint64_t)15);
+    dstr_off[t + 1] = dstr_off[t] + ql + wl + 16;
+  }
+  if (dir_off[ntask] > (4ull << 30)) return fail(SMALTGPU_EARG, "direction matrices above 4 GiB");
+  std::vector<uint8_t> wdec(r_off[ntask] + 1);                       // window codes as the mapper decodes them (ref_code)
+  for (size_t o = 0; o < r_off[ntask]; o++) { const uint8_t c = rcodes[o] & 7; wdec[o] = c == 7 ? 0 : ((c == 6 || c == 4) ? 5 : c); }
+  HIPCHK(hipSetDevice(m->device));
+  const bool strip = form == (int)BF_STRIP8 || form == (int)BF_STRIP16;
+  const uint32_t rowlen = qmaxlen + rmaxlen + 2;
+  const size_t nbnd = strip ? (size_t)ntask * 2 * rmaxlen : 1, nrows = form == (int)BF_SCALAR ? (size_t)ntask * 2 * rowlen : 1;
+  uint8_t *dq = nullptr, *dw = nullptr, *ddir = nullptr, *dtmp = nullptr, *dds = nullptr;
+  uint32_t *dqo = nullptr, *dro = nullptr, *ddso = nullptr; uint64_t *ddo = nullptr; int32_t *dbd = nullptr, *div = nullptr;
+  int2 *dbnd = nullptr; int *drows = nullptr; BandNodeOut *dout = nullptr;
+  int rv = 0;
+  if (dalloc(&dq, q_off[ntask] + 16) || dalloc(&dw, r_off[ntask] + 16) || dalloc(&ddir, dir_off[ntask] + 16) || dalloc(&dtmp, (size_t)dstr_off[ntask] + 16) ||
+      dalloc(&dds, (size_t)dstr_off[ntask] + 16) || dalloc(&dqo, (size_t)ntask + 1) || dalloc(&dro, (size_t)ntask + 1) || dalloc(&ddso, (size_t)ntask + 1) ||
+      dalloc(&ddo, (size_t)ntask + 1) || dalloc(&dbd, 4 * (size_t)ntask + 4) || dalloc(&div, 2 * (size_t)ntask + 2) || dalloc(&dbnd, nbnd) ||
+      dalloc(&drows, nrows) || dalloc(&dout, (size_t)ntask + 1)) rv = SMALTGPU_ENOMEM;
+  if (!rv) {
+    (void)hipMemcpy(dq, qcodes, q_off[ntask], hipMemcpyHostToDevice);
+    (void)hipMemcpy(dw, wdec.data(), r_off[ntask], hipMemcpyHostToDevice);
+    (void)hipMemcpy(dqo, q_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dro, r_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(ddso, dstr_off.data(), ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(ddo, dir_off.data(), ((size_t)ntask + 1) * 8, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dbd, band, (size_t)ntask * 16, hipMemcpyHostToDevice);
+    (void)hipMemcpy(div, iv, (size_t)ntask * 8, hipMemcpyHostToDevice);
+    (void)hipMemset(ddir, 0, dir_off[ntask] + 16);
+    (void)hipMemset(dds, 0, (size_t)dstr_off[ntask] + 16);
+    (void)hipMemset(drows, 0, nrows * sizeof(int));
+    (void)hipMemset(dbnd, 0, nbnd * sizeof(int2));
+    BandNodeArgs a;
+    a.q = dq; a.q_off = dqo; a.win = dw; a.r_off = dro; a.ntask = ntask; a.band = dbd; a.iv = div;
+    a.minscore = minscore; a.form = form; a.lds = lds; a.tw = tw;
+    a.dir = ddir; a.dir_off = ddo; a.bnd = dbnd; a.bndcap = rmaxlen; a.rows = drows; a.rowlen = rowlen;
+    a.dtmp = dtmp; a.dstr = dds; a.dstr_off = ddso; a.out = dout;
+    if (launch_band_nodes(m->stream, a, p)) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
+    else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
+    else {
+      (void)hipMemcpy(out, dout, (size_t)ntask * sizeof(BandNodeOut), hipMemcpyDeviceToHost);
+      (void)hipMemcpy(dstr, dds, dstr_off[ntask], hipMemcpyDeviceToHost);
+    }
+  }
+  (void)hipFree(dq); (void)hipFree(dw); (void)hipFree(ddir); (void)hipFree(dtmp); (void)hipFree(dds); (void)hipFree(dqo); (void)hipFree(dro);
+  (void)hipFree(ddso); (void)hipFree(ddo); (void)hipFree(dbd); (void)hipFree(div); (void)hipFree(dbnd); (void)hipFree(drows); (void)hipFree(dout);
   return rv;
 }
 

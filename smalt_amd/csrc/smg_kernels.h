@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include "smg_cands.hpp"
+#include "smg_bandnode.h"
 
 namespace smg {
 
@@ -39,6 +40,17 @@ int launch_sw_full(hipStream_t s, const Batch &b, const DevIndex &ix, const MapP
 int launch_sw_strip(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, void *bnd, uint8_t *win, uint32_t wcap, uint32_t grid);
 int launch_sw_strip_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n, const MapPar &p,
                         int32_t *sc, void *bnd, uint8_t *win, uint32_t wcap, uint32_t grid);
+// stand-alone packed strip kernel (pairs of tasks); -2: penalties or the longest read's score beyond its 16-bit halves
+int launch_sw_strip16_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n, const MapPar &p,
+                          int32_t *sc, void *bnd, uint8_t *win, uint32_t wcap, uint32_t grid, uint32_t qmax_len);
+// stand-alone K2b: band = n x {band_l, band_r, qs, qe}, windows in the index's packed layout at the base offsets ro;
+// band_fast_wave (one wave per task) and band_fast_scalar (one lane per task, rows: n x 2 x rowlen ints)
+int launch_sw_band_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint32_t *packed, const uint32_t *ro, uint32_t n,
+                       const MapPar &p, const int32_t *band, int32_t *sc, void *bnd, uint8_t *win, uint32_t wcap, uint32_t grid);
+int launch_sw_band_scalar_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint32_t *packed, const uint32_t *ro, uint32_t n,
+                              const MapPar &p, const int32_t *band, int32_t *sc, int *rows, uint32_t rowlen);
+// stand-alone K3 nodes, one wave per task in the form a.form (smg_bandnode.hip); the caller has checked the form's precondition
+int launch_band_nodes(hipStream_t s, const BandNodeArgs &a, const MapPar &p);
 int launch_sw_scalar(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, int *rows, uint32_t rowlen, uint32_t nthreads,
                      uint32_t qmax_len);
 int launch_sw_full_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n,

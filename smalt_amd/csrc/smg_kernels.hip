@@ -1441,6 +1441,60 @@ __global__ void __launch_bounds__(64) k_sw_strip_raw(const uint8_t *qcodes, cons
   }
 }
 
+// stand-alone form of the packed strip kernel: tasks 2t, 2t+1 share a wave as the list entries of k_sw_strip16 do; a read
+// with non-ACGT codes reports -2 (production leaves it to k_sw_strip), a window above wcap -1, and the partner runs on
+template <bool M3>
+__global__ void __launch_bounds__(64) k_sw_strip16_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes, const uint32_t *r_off,
+                                                       uint32_t ntask, MapPar p, int32_t *scores, uint2 *bnd_all, uint16_t *win_all, uint32_t wcap) {
+  __shared__ uint32_t rowtab[8];
+  __shared__ uint2 ring[256];
+  const Sw16Par sp = sw16_par(p);
+  sw16_rowtab(rowtab, sp);
+  __syncthreads();
+  const uint32_t npair = (ntask + 1) / 2;
+  uint2 *bnd = bnd_all + (size_t)blockIdx.x * 2 * wcap;
+  uint16_t *win = win_all + (size_t)blockIdx.x * wcap;
+  for (uint32_t tp = blockIdx.x; tp < npair; tp += gridDim.x) {
+    bool live[2] = {false, false}, qn[2] = {false, false};
+    uint32_t qlen[2] = {0, 0}, wlen[2] = {0, 0};
+    const uint8_t *q[2] = {qcodes, qcodes}, *r[2] = {rcodes, rcodes};
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const uint32_t t = 2 * tp + (uint32_t)u;
+      if (t < ntask) {
+        qlen[u] = q_off[t + 1] - q_off[t]; wlen[u] = r_off[t + 1] - r_off[t];
+        q[u] += q_off[t]; r[u] += r_off[t];
+        bool bad = false;
+        for (uint32_t j = threadIdx.x; j < qlen[u]; j += 64) bad |= (q[u][j] & 4) != 0;
+        qn[u] = __any(bad);
+        live[u] = wlen[u] <= wcap && !qn[u];
+      }
+      if (!live[u]) { qlen[u] = 0; wlen[u] = 0; }
+    }
+    const uint32_t wmax = wlen[0] > wlen[1] ? wlen[0] : wlen[1];
+    uint32_t bb = 0;
+    if (wmax) {                                                  // wave-uniform
+      __syncthreads();
+      for (uint32_t i = threadIdx.x; i < wmax; i += 64) {
+        uint32_t cd[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) { const uint32_t x = i < wlen[u] ? (r[u][i] & 7u) : 5u; cd[u] = x == 7 ? 0 : ((x == 6 || x == 4) ? 5 : x); }
+        win[i] = (uint16_t)(cd[0] | (cd[1] << 8));
+      }
+      __threadfence();
+      __syncthreads();
+      bb = sw_strip16_core<M3>(q[0], qlen[0], q[1], qlen[1], win, wmax, bnd, wcap, rowtab, ring, sp);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int u = 0; u < 2; u++) {
+        const uint32_t t = 2 * tp + (uint32_t)u;
+        if (t < ntask) scores[t] = live[u] ? (int)((bb >> (16 * u)) & 0xffffu) : (qn[u] ? -2 : -1);
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // K2b (alignSmiWatBandFast, alignment.c:1029-1233) for long reads: one wave per task, the strip scheme of
 // sw_strip_core with the restricted cell update and the band as an activity mask.  Row r of the band visits the
@@ -1604,6 +1658,52 @@ __global__ void __launch_bounds__(64) k_sw_scalar(Batch b, DevIndex ix, MapPar p
     b.rcpool[t].swscor = c.swscor;
     b.rcpool[t].flags = c.flags | RCF_SCORED;
   }
+}
+
+// stand-alone K2b over explicit reads and a packed array of windows (parity tests): band[t] = {band_l, band_r, qs, qe};
+// a band that band_init refuses keeps score 0 (the host reports it in the status).  One wave per task, as k_sw_band ...
+__global__ void __launch_bounds__(64) k_sw_band_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint32_t *packed, const uint32_t *r_off,
+                                                    uint32_t ntask, MapPar p, const int4 *band, int32_t *scores, int2 *bnd_all, uint8_t *win_all,
+                                                    uint32_t wcap) {
+  __shared__ uint2 tab[8];
+  __shared__ int2 ring[256];
+  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
+  sw_tab8(tab, p, bias);
+  __syncthreads();
+  int2 *bnd = bnd_all + (size_t)blockIdx.x * 2 * wcap;
+  uint8_t *win = win_all + (size_t)blockIdx.x * wcap;
+  for (uint32_t t = blockIdx.x; t < ntask; t += gridDim.x) {
+    const uint32_t qlen = q_off[t + 1] - q_off[t], wlen = r_off[t + 1] - r_off[t];
+    const int4 bd4 = band[t];
+    Band bd;
+    if (wlen > wcap || band_init(bd, bd4.x, bd4.y, bd4.z, bd4.w, (int)qlen, 0, (int)wlen - 1, (int)wlen)) {     // wave-uniform
+      if (threadIdx.x == 0) scores[t] = 0;
+      continue;
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < wlen; i += 64) win[i] = (uint8_t)ref_code(packed, (uint64_t)r_off[t] + i);
+    __threadfence();
+    __syncthreads();
+    const int best = band_fast_wave(bd, qcodes + q_off[t], win, bnd, wcap, tab, ring, bias, -p.gap_init, -p.gap_ext);
+    if (threadIdx.x == 0) scores[t] = best;
+  }
+}
+
+// ... and one lane per task, as the banded tasks of k_sw_scalar; rows: 2 x rowlen ints per lane
+__global__ void __launch_bounds__(64) k_sw_band_scalar_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint32_t *packed, const uint32_t *r_off,
+                                                           uint32_t ntask, MapPar p, const int4 *band, int32_t *scores, int *rows, uint32_t rowlen) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ntask) return;
+  int *Hp = rows + (size_t)t * 2 * rowlen, *Ep = Hp + rowlen;
+  int8_t M[64];
+  score_matrix(M, p.match, p.mismatch);
+  const uint32_t qlen = q_off[t + 1] - q_off[t], wlen = r_off[t + 1] - r_off[t];
+  const int4 bd4 = band[t];
+  Band bd;
+  int best = 0;
+  if (!band_init(bd, bd4.x, bd4.y, bd4.z, bd4.w, (int)qlen, 0, (int)wlen - 1, (int)wlen))
+    best = band_fast_scalar(bd, qcodes + q_off[t], packed, (uint64_t)r_off[t], M, -p.gap_init, -p.gap_ext, Hp, Ep);
+  scores[t] = best;
 }
 
 // stand-alone K2a over explicit (query, window) code arrays -- parity tests of the kernel
@@ -1794,6 +1894,9 @@ static bool sw16_ok(const MapPar &p) {
          -p.gap_init >= 0 && -p.gap_init < 30000 && -p.gap_ext >= 0 && -p.gap_ext < 30000;
 }
 
+// the packed strip kernel's max3 form: every value of the longest read stays below the half-float infinity pattern
+static bool sw_strip16_max3(uint32_t qmax_len, int match) { return (uint64_t)qmax_len * (uint64_t)match + 512 < 0x7C00ull; }
+
 // test hooks: SMALTGPU_SW16_ROWFRAME=0 keeps the packed sweep in its forms without any frame (sw16f_core, sw16_core),
 // SMALTGPU_SW16_PAIRFRAME=0 gives the row frame wherever it applies, so that the forms can be compared on the same tasks;
 // read at every launch, which lets one process run all three.  Bit 0: row frame, bit 1: pair frame.
@@ -1838,7 +1941,7 @@ int launch_sw_strip(hipStream_t s, const Batch &b, const DevIndex &ix, const Map
   if (!b.nreads || !grid) return 0;
   if (sw16_ok(p) && (uint64_t)b.qmax * (uint64_t)p.match < 60000ull)          // 16-bit halves hold every score of these reads
   {
-    if ((uint64_t)b.qmax * (uint64_t)p.match + 512 < 0x7C00ull)                 // every value below the half-float infinity pattern: max3 form
+    if (sw_strip16_max3(b.qmax, p.match))
       hipLaunchKernelGGL(k_sw_strip16<true>, dim3(grid), dim3(64), 0, s, b, ix, p, (uint2 *)bnd, (uint16_t *)win, wcap);
     else hipLaunchKernelGGL(k_sw_strip16<false>, dim3(grid), dim3(64), 0, s, b, ix, p, (uint2 *)bnd, (uint16_t *)win, wcap);
   }
@@ -1852,6 +1955,36 @@ int launch_sw_strip_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, con
                         int32_t *sc, void *bnd, uint8_t *win, uint32_t wcap, uint32_t grid) {
   if (!n) return 0;
   hipLaunchKernelGGL(k_sw_strip_raw, dim3(n < grid ? n : grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc, (int2 *)bnd, win, wcap);
+  SMG_LAUNCH_CHECK();
+  return 0;
+}
+
+// -2: the penalties or the longest read's score do not fit 16-bit halves (the rule of launch_sw_strip, no fall-back here)
+int launch_sw_strip16_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n, const MapPar &p,
+                          int32_t *sc, void *bnd, uint8_t *win, uint32_t wcap, uint32_t grid, uint32_t qmax_len) {
+  if (!n) return 0;
+  if (!sw16_ok(p) || (uint64_t)qmax_len * (uint64_t)p.match >= 60000ull) return -2;
+  const uint32_t npair = (n + 1) / 2;
+  const dim3 g(npair < grid ? npair : grid);
+  if (sw_strip16_max3(qmax_len, p.match))
+    hipLaunchKernelGGL(k_sw_strip16_raw<true>, g, dim3(64), 0, s, q, qo, r, ro, n, p, sc, (uint2 *)bnd, (uint16_t *)win, wcap);
+  else hipLaunchKernelGGL(k_sw_strip16_raw<false>, g, dim3(64), 0, s, q, qo, r, ro, n, p, sc, (uint2 *)bnd, (uint16_t *)win, wcap);
+  SMG_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_sw_band_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint32_t *packed, const uint32_t *ro, uint32_t n,
+                       const MapPar &p, const int32_t *band, int32_t *sc, void *bnd, uint8_t *win, uint32_t wcap, uint32_t grid) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(k_sw_band_raw, dim3(n < grid ? n : grid), dim3(64), 0, s, q, qo, packed, ro, n, p, (const int4 *)band, sc, (int2 *)bnd, win, wcap);
+  SMG_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_sw_band_scalar_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint32_t *packed, const uint32_t *ro, uint32_t n,
+                              const MapPar &p, const int32_t *band, int32_t *sc, int *rows, uint32_t rowlen) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(k_sw_band_scalar_raw, dim3((n + 63) / 64), dim3(64), 0, s, q, qo, packed, ro, n, p, (const int4 *)band, sc, rows, rowlen);
   SMG_LAUNCH_CHECK();
   return 0;
 }
