@@ -622,6 +622,38 @@ int smaltgpu_sw_pairframe_max_steps(int match, int mismatch, int gap_init, int g
 int smaltgpu_rank_sort_batch(smaltgpu_mapper *m, const uint32_t *keys, const uint32_t *off, uint32_t narr, int nneed, int in_lds,
                              uint32_t *out_keys, uint32_t *out_idx);
 
+/* S3 on its own (kernel k_hits): the reads are uploaded and the launches of a mapping call run up to and including k_hits
+ * (encode, seed, hits -- the mapper's own launchers, geometry and buffers, no other kernel); what the kernel left behind comes
+ * back in host copies owned by the mapper, valid until its next call.  Indexed by rs = 2 * read + strand; `stride` entries
+ * per strand in seeds and qmask. */
+enum { SMALTGPU_HITRUN_NONE = 0,     /* the candidate stage gathers and sorts this strand itself */
+       SMALTGPU_HITRUN_SORTED = 1,   /* pool[off .. off + n) holds the strand's keys in ascending order */
+       SMALTGPU_HITRUN_OVERFLOW = 2  /* the pool was full: a mapping call re-maps the read in a smaller batch */ };
+typedef struct smaltgpu_hit_seed { uint32_t posidx, nhits, qoffs; } smaltgpu_hit_seed;
+typedef struct smaltgpu_hit_run { uint64_t off; uint32_t n, mode; } smaltgpu_hit_run;
+typedef struct smaltgpu_hits_out {
+  uint32_t nstrands, stride;         /* 2 * nreads; entries per strand of seeds and qmask */
+  uint32_t window, tab;              /* keys per window and entries of the per-list tables the kernel ran with */
+  const uint32_t *n_seeds, *seed_rank, *status;   /* [nstrands] hit info of the seeding stage */
+  const smaltgpu_hit_seed *seeds;    /* [nstrands][stride] */
+  const uint8_t *qmask;              /* [nstrands][stride] hit qualifier per read offset, after k_hits */
+  const smaltgpu_hit_run *runs;      /* [nstrands] */
+  uint64_t hit_count;                /* keys reserved in the pool by all strands (may exceed pool_cap) */
+  uint64_t pool_cap;                 /* capacity the kernel ran with */
+  const uint64_t *pool;              /* the first min(hit_count, pool_cap) keys of the pool */
+} smaltgpu_hits_out;
+/* window: keys per window for this call (clamped to 256..1024 as at mapper creation), 0 = the mapper's; pool_keys: capacity of
+ * the pool for this call, 0 = the mapper's (SMALTGPU_EARG above the allocation).  SMALTGPU_EARG for a mapper that keeps S3
+ * inside the candidate stage (max_read_len > 248, that is a stride of more than 256 read offsets, or SMALTGPU_HITS_SPLIT=0) and
+ * for a batch above the mapper's capacity. */
+int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
+                        const smaltgpu_params *par, uint32_t window, uint64_t pool_keys, smaltgpu_hits_out *out);
+
+/* The 64-bit key sorts of the candidate stage, one wave per array (array t in keys[off[t]..off[t+1])): the array is copied to
+ * LDS, sorted and copied out.  form 0, 1, 2: the register network over 4, 8, 16 keys per lane (arrays of at most 256, 512,
+ * 1024 keys); form 3: the network in LDS (at most 1024 keys).  SMALTGPU_EARG for a longer array. */
+int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out);
+
 const char *smaltgpu_last_error(void);
 int smaltgpu_device_count(void);
 

@@ -126,6 +126,16 @@ class BandNode(C.Structure):           # smaltgpu_band_node
                 ("rs", C.c_int32), ("dlen", C.c_int32), ("stroffs", C.c_uint32)]
 
 
+class HitsOut(C.Structure):            # smaltgpu_hits_out
+    _fields_ = [("nstrands", C.c_uint32), ("stride", C.c_uint32), ("window", C.c_uint32), ("tab", C.c_uint32),
+                ("n_seeds", C.POINTER(C.c_uint32)), ("seed_rank", C.POINTER(C.c_uint32)), ("status", C.POINTER(C.c_uint32)),
+                ("seeds", C.c_void_p), ("qmask", C.c_void_p), ("runs", C.c_void_p),
+                ("hit_count", C.c_uint64), ("pool_cap", C.c_uint64), ("pool", C.c_void_p)]
+
+
+HITRUN_NONE, HITRUN_SORTED, HITRUN_OVERFLOW = 0, 1, 2          # SMALTGPU_HITRUN_*
+SORT_REG4, SORT_REG8, SORT_REG16, SORT_LDS = 0, 1, 2, 3        # forms of smaltgpu_sort_u64_batch
+
 # SMALTGPU_BAND_*: the forms of the K3 band pass (smaltgpu_band_align_nodes)
 BAND_ROWS, BAND_ANTIDIAG, BAND_WAVE2, BAND_WAVE4, BAND_WAVE7, BAND_WAVE12, BAND_STRIP8, BAND_STRIP16, BAND_SCALAR = range(9)
 NODE_ALIGNED, NODE_REFUSED, NODE_BELOW = 0, 1, 2
@@ -237,6 +247,9 @@ def lib():
         L.smaltgpu_sw_rowframe_max_steps.argtypes = [C.c_int] * 5
         L.smaltgpu_sw_pairframe_max_steps.argtypes = [C.c_int] * 5
         L.smaltgpu_rank_sort_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.smaltgpu_hits_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.c_uint32, C.c_uint64,
+                                          C.POINTER(HitsOut)]
+        L.smaltgpu_sort_u64_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.smaltgpu_sample_interval.argtypes = [C.c_uint64, C.c_int]
         L.smaltgpu_inshist_from_sample.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_uint64]
         L.smaltgpu_inshist_read.argtypes = [C.POINTER(C.c_void_p), C.c_char_p]
@@ -702,3 +715,39 @@ class Mapper:
         _check(lib().smaltgpu_rank_sort_batch(self.h, keys.ctypes.data, off.ctypes.data, len(arrays), nneed, int(in_lds),
                                               ok.ctypes.data, oi.ctypes.data))
         return [(ok[off[t]:off[t + 1]], oi[off[t]:off[t + 1]]) for t in range(len(arrays))]
+
+    def hits_batch(self, reads: Sequence[bytes], quals: Optional[Sequence[bytes]], params: Params, window: int = 0, pool_keys: int = 0):
+        """Stand-alone S3 (smaltgpu_hits_batch): encode, seed and k_hits over the reads, nothing else.  -> dict of numpy copies,
+        per strand rs = 2 * read + strand: n_seeds, seed_rank, status, seeds[rs] (posidx, nhits, qoffs), qmask[rs], run_off,
+        run_n, run_mode; and hit_count, pool_cap, pool, window, tab."""
+        import numpy as np
+        bases, q, off = self._pack(reads, quals)
+        out = HitsOut()
+        _check(lib().smaltgpu_hits_batch(self.h, bases, q, off, len(reads), C.byref(params), window, pool_keys, C.byref(out)))
+        ns, stride = out.nstrands, out.stride
+
+        def arr(ptr, dtype, count):
+            if not count:
+                return np.zeros(0, dtype=dtype)
+            nbytes = count * np.dtype(dtype).itemsize
+            return np.frombuffer(C.string_at(ptr, nbytes), dtype=dtype).copy()
+        seeds = arr(out.seeds, np.uint32, ns * stride * 3).reshape(ns, stride, 3)
+        runs = arr(out.runs, np.dtype([("off", np.uint64), ("n", np.uint32), ("mode", np.uint32)]), ns)
+        return dict(n_seeds=arr(C.cast(out.n_seeds, C.c_void_p), np.uint32, ns), seed_rank=arr(C.cast(out.seed_rank, C.c_void_p), np.uint32, ns),
+                    status=arr(C.cast(out.status, C.c_void_p), np.uint32, ns), seeds=seeds, qmask=arr(out.qmask, np.uint8, ns * stride).reshape(ns, stride),
+                    run_off=runs["off"].copy(), run_n=runs["n"].copy(), run_mode=runs["mode"].copy(), hit_count=int(out.hit_count),
+                    pool_cap=int(out.pool_cap), pool=arr(out.pool, np.uint64, min(int(out.hit_count), int(out.pool_cap))),
+                    window=int(out.window), tab=int(out.tab), stride=int(stride))
+
+    def sort_u64_batch(self, arrays, form: int):
+        """Stand-alone 64-bit key sorts (smaltgpu_sort_u64_batch): list of uint64 numpy arrays -> list of sorted arrays.
+        form: SORT_REG4 / SORT_REG8 / SORT_REG16 (register network, at most 256 / 512 / 1024 keys) or SORT_LDS."""
+        import numpy as np
+        off = np.zeros(len(arrays) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(a) for a in arrays])
+        keys = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros(0), dtype=np.uint64)
+        if keys.size == 0:
+            keys = np.zeros(1, dtype=np.uint64)
+        out = np.zeros(keys.size, dtype=np.uint64)
+        _check(lib().smaltgpu_sort_u64_batch(self.h, keys.ctypes.data, off.ctypes.data, len(arrays), form, out.ctypes.data))
+        return [out[off[t]:off[t + 1]] for t in range(len(arrays))]

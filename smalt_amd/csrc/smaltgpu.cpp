@@ -436,6 +436,9 @@ struct smaltgpu_mapper {
   std::vector<HitInfoHdr> h_hi;
   bool last_fine = false;
   uint64_t remap_batches = 0;               // device batches smaltgpu_map_batch ran to recover from pool overflows (diagnostic)
+  // host copies of what k_hits left behind (smaltgpu_hits_batch, test entry)
+  struct HitsHost { std::vector<HitInfoHdr> hi; std::vector<uint32_t> n_seeds, seed_rank, status; std::vector<SeedRec> seeds; std::vector<uint8_t> qmask;
+                    std::vector<HitRun> runs; std::vector<uint64_t> pool; } hh;
   hipEvent_t ev[T_NUM + 1] = {nullptr};
   double ms[T_NUM] = {0};
   unsigned long long work[WK_NWORK] = {0};
@@ -1475,5 +1478,95 @@ extern "C" int smaltgpu_rank_sort_batch(smaltgpu_mapper *m, const uint32_t *keys
     else { (void)hipMemcpy(out_keys, dok, tot * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(out_idx, doi, tot * 4, hipMemcpyDeviceToHost); }
   }
   (void)hipFree(dk); (void)hipFree(doff); (void)hipFree(dkv); (void)hipFree(dok); (void)hipFree(doi);
+  return rv;
+}
+
+// S3 on its own: the launches of run_pipeline up to and including k_hits, on the mapper's buffers, and host copies of what they left
+extern "C" int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
+                                   const smaltgpu_params *par, uint32_t window, uint64_t pool_keys, smaltgpu_hits_out *out) {
+  static_assert(sizeof(SeedRec) == sizeof(smaltgpu_hit_seed) && sizeof(HitRun) == sizeof(smaltgpu_hit_run), "hit record layout");
+  static_assert((uint32_t)HITRUN_NONE == (uint32_t)SMALTGPU_HITRUN_NONE && (uint32_t)HITRUN_SORTED == (uint32_t)SMALTGPU_HITRUN_SORTED &&
+                (uint32_t)HITRUN_OVERFLOW == (uint32_t)SMALTGPU_HITRUN_OVERFLOW, "hit run modes");
+  if (!m || !bases || !read_off || !par || !out) return fail(SMALTGPU_EARG, "null argument");
+  if (!m->hits_W || !m->b_hitrun) return fail(SMALTGPU_EARG, "this mapper keeps S3 inside the candidate stage (max_read_len > 248 or SMALTGPU_HITS_SPLIT=0)");
+  if (nreads > m->max_reads || read_off[nreads] - read_off[0] > m->max_bases) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity");
+  if (pool_keys > m->b.hitpool_cap) return fail(SMALTGPU_EARG, "pool_keys exceeds the pool's allocation (%llu keys)", (unsigned long long)m->b.hitpool_cap);
+  int rv = check_par(m, par);
+  if (rv) return rv;
+  uint32_t W = window ? window : m->hits_W;
+  if (W < 256) W = 256;
+  if (W > 1024) W = 1024;
+  const uint64_t cap = pool_keys ? pool_keys : m->b.hitpool_cap;
+  const uint64_t total = read_off[nreads] - read_off[0];
+  m->h_off.resize((size_t)nreads + 1);
+  for (uint32_t i = 0; i <= nreads; i++) {
+    m->h_off[i] = read_off[i] - read_off[0];
+    if (i && m->h_off[i] - m->h_off[i - 1] > m->max_len) return fail(SMALTGPU_EARG, "read %u is longer than the mapper's max_read_len", i - 1);
+  }
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  if (total) HIPCHK(hipMemcpyAsync(m->d_bases, bases + read_off[0], total, hipMemcpyHostToDevice, s));
+  if (quals && total) HIPCHK(hipMemcpyAsync(m->d_quals, quals + read_off[0], total, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(m->d_off, m->h_off.data(), ((size_t)nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  // the batch as run_pipeline sets it up for a plain call
+  Batch &b = m->b;
+  const DevIndex &d = m->ix->d;
+  const MapPar p = to_par(par);
+  b.iv_off = nullptr; b.iv = nullptr; b.min_sw = nullptr; b.prevmax = nullptr; b.fine_idx = nullptr; b.fine_pos = nullptr; b.fine_off = nullptr;
+  b.alloc_len = nullptr; b.seed_range = nullptr; b.totals_only = 0; b.raw_results = 0;
+  m->last_fine = false; m->last_par = p; m->last_n = nreads; m->have_host_off = true; m->fetch_open = false;
+  b.nreads = nreads; b.codes = m->d_codes; b.codes_rc = m->d_codes_rc; b.qual = quals ? m->d_quals : nullptr; b.read_off = m->d_off;
+  b.hitrun = m->b_hitrun;
+  Batch hb = b;
+  hb.hitpool_cap = cap;                                   // this call only
+  HIPCHK(hipMemsetAsync(m->d_counters, 0, smaltgpu_mapper::CT_BYTES, s));
+  rv = launch_encode(s, m->d_bases, m->d_off, nreads, m->d_codes, m->d_codes_rc);
+  if (!rv) rv = launch_seed(s, hb, d, p, m->seed_scr, m->seed_bytes, m->seed_slots);
+  if (!rv) rv = launch_hits(s, hb, d, p, W, m->cg.tab, m->hits_wg);
+  if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
+  HIPCHK(hipStreamSynchronize(s));
+  smaltgpu_mapper::HitsHost &h = m->hh;
+  const size_t ns = 2 * (size_t)nreads, stride = m->qmax;
+  h.hi.resize(ns ? ns : 1); h.n_seeds.assign(ns ? ns : 1, 0); h.seed_rank.assign(ns ? ns : 1, 0); h.status.assign(ns ? ns : 1, 0);
+  h.seeds.resize(ns * stride + 1); h.qmask.resize(ns * stride + 1); h.runs.resize(ns ? ns : 1);
+  unsigned long long count = 0;
+  if (ns) {
+    HIPCHK(hipMemcpy(h.hi.data(), b.hi, ns * sizeof(HitInfoHdr), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.seeds.data(), b.seeds, ns * stride * sizeof(SeedRec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.qmask.data(), b.qmask, ns * stride, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.runs.data(), m->b_hitrun, ns * sizeof(HitRun), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&count, b.hit_count, sizeof(count), hipMemcpyDeviceToHost));
+  }
+  for (size_t i = 0; i < ns; i++) { h.n_seeds[i] = h.hi[i].n_seeds; h.seed_rank[i] = h.hi[i].seed_rank; h.status[i] = h.hi[i].status; }
+  const uint64_t npool = count < cap ? count : cap;
+  h.pool.resize(npool ? npool : 1);
+  if (npool) HIPCHK(hipMemcpy(h.pool.data(), b.hitpool, npool * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  memset(out, 0, sizeof(*out));
+  out->nstrands = (uint32_t)ns; out->stride = (uint32_t)stride; out->window = W; out->tab = m->cg.tab;
+  out->n_seeds = h.n_seeds.data(); out->seed_rank = h.seed_rank.data(); out->status = h.status.data();
+  out->seeds = (const smaltgpu_hit_seed *)h.seeds.data(); out->qmask = h.qmask.data(); out->runs = (const smaltgpu_hit_run *)h.runs.data();
+  out->hit_count = count; out->pool_cap = cap; out->pool = h.pool.data();
+  return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out) {
+  if (!m || !keys || !off || !out) return fail(SMALTGPU_EARG, "null argument");
+  if (form < 0 || form > 3) return fail(SMALTGPU_EARG, "unknown form %d", form);
+  const uint32_t nmax = form == 0 ? 256u : (form == 1 ? 512u : 1024u);
+  for (uint32_t t = 0; t < narr; t++) if (off[t + 1] < off[t] || off[t + 1] - off[t] > nmax) return fail(SMALTGPU_EARG, "array %u does not fit form %d (at most %u keys)", t, form, nmax);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t tot = narr ? off[narr] : 0;
+  uint64_t *dk = nullptr, *dout = nullptr;
+  uint32_t *doff = nullptr;
+  int rv = 0;
+  if (dalloc(&dk, tot + 1) || dalloc(&dout, tot + 1) || dalloc(&doff, (size_t)narr + 1)) rv = SMALTGPU_ENOMEM;
+  if (!rv) {
+    if (tot) (void)hipMemcpy(dk, keys, tot * 8, hipMemcpyHostToDevice);
+    (void)hipMemcpy(doff, off, ((size_t)narr + 1) * 4, hipMemcpyHostToDevice);
+    if (launch_sort_u64_raw(m->stream, dk, doff, narr, form, dout)) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
+    else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
+    else if (tot) (void)hipMemcpy(out, dout, tot * 8, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dk); (void)hipFree(dout); (void)hipFree(doff);
   return rv;
 }

@@ -2030,6 +2030,37 @@ int launch_rank_sort_raw(hipStream_t s, const uint32_t *keys, const uint32_t *of
   return 0;
 }
 
+// test entry of the 64-bit key sorts (smg_exec.h): one wave per array, the array in LDS behind an LDS-typed pointer as in
+// k_hits and k_cands (the host checks that every array fits the form: n <= 64 * E, n <= 1024)
+__global__ void __launch_bounds__(64) k_sort_u64_raw(const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out) {
+  __shared__ __align__(16) uint64_t sh[1024];
+  typedef typename ptr_of<uint64_t, true>::type P64;
+  P64 a = (P64)sh;
+  for (uint32_t t = blockIdx.x; t < narr; t += gridDim.x) {
+    const uint32_t o = off[t];
+    uint32_t n = off[t + 1] - o;
+    if (n > 1024u) n = 1024u;
+    for (uint32_t i = threadIdx.x; i < n; i += 64) a[i] = keys[o + i];
+    __syncthreads();
+#if defined(__HIP_DEVICE_COMPILE__)      // (the register forms exist in the device pass only)
+    if (form == 0) wave_sort_u64_reg<4>(a, n);
+    else if (form == 1) wave_sort_u64_reg<8>(a, n);
+    else if (form == 2) wave_sort_u64_reg<16>(a, n);
+    else wave_sort_u64(a, n);
+#endif
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += 64) out[o + i] = a[i];
+    __syncthreads();
+  }
+}
+
+int launch_sort_u64_raw(hipStream_t s, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out) {
+  if (!narr) return 0;
+  hipLaunchKernelGGL(k_sort_u64_raw, dim3(narr < 4096 ? narr : 4096), dim3(64), 0, s, keys, off, narr, form, out);
+  SMG_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_sw_full_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n,
                        const MapPar &p, int32_t *sc, uint32_t qmax_len, int packed16) {
   int G, C;

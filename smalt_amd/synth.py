@@ -17,10 +17,12 @@ DEFAULT_SEED = 20261004
 
 
 def make_reference(nchr: int, chrlen: int, seed: int = DEFAULT_SEED, repeat_frac: float = 0.15,
-                   n_fam: int = 50, cons_len: int = 300, divergence: float = 0.08):
-    """Return a list of `nchr` uint8 code arrays (values 0..3) of length `chrlen`."""
+                   n_fam: int = 50, cons_len: int = 300, divergence: float = 0.08, return_families: bool = False):
+    """Return a list of `nchr` uint8 code arrays (values 0..3) of length `chrlen`; with return_families also the consensus
+    sequences of the repeat families, an (n_fam, cons_len) array (empty when no repeats were placed)."""
     rng = np.random.default_rng(seed)
     chroms = [rng.integers(0, 4, size=chrlen, dtype=np.uint8) for _ in range(nchr)]
+    fams = np.zeros((0, cons_len), dtype=np.uint8)
     if repeat_frac > 0 and chrlen > 4 * cons_len:
         fams = rng.integers(0, 4, size=(n_fam, cons_len), dtype=np.uint8)
         ncopies = int(repeat_frac * chrlen / cons_len)
@@ -32,7 +34,7 @@ def make_reference(nchr: int, chrlen: int, seed: int = DEFAULT_SEED, repeat_frac
             copies = np.where(mut, (copies + rng.integers(1, 4, size=copies.shape)) & 3, copies)
             idx = starts[:, None] + np.arange(cons_len)[None, :]
             c[idx.ravel()] = copies.ravel().astype(np.uint8)
-    return chroms
+    return (chroms, fams) if return_families else chroms
 
 
 def revcomp_codes(codes: np.ndarray) -> np.ndarray:

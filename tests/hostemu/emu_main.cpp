@@ -58,6 +58,7 @@ int main(int argc, char **argv) {
   p.min_basq = minbasq; p.target_depth = 512; p.max_depth = 2048;
   p.flags = (scordiff ? 0 : FLG_BEST) | (ix.nseq < 512 ? FLG_SEQBYSEQ : 0) | (xflag ? (FLG_NOSHRTINFO | FLG_SENSITIVE) : 0);
   p.match = 1; p.mismatch = -2; p.gap_init = -4; p.gap_ext = -3;
+  if (getenv("EMU_CONCAT") && atoi(getenv("EMU_CONCAT")) != 0) p.flags &= ~(uint32_t)FLG_SEQBYSEQ;   // one hit list over all sequences, as for >= 512 of them
 
   // ---- read the FASTQ into one batch ----
   std::vector<std::string> names;
@@ -133,9 +134,15 @@ int main(int argc, char **argv) {
   std::vector<uint64_t> hitpool(split ? (size_t)n * 2 * hcap_strand / 8 + (1u << 20) : 1);
   std::vector<HitRun> hitrun((size_t)2 * n + 1);
   unsigned long long hit_count = 0;
+  // EMU_HITS_TAB: entries of the per-list tables of stage_hits (a mapper sets them from its longest read: qmax + 8, at most CANDS_TAB)
+  uint32_t hitsTab = getenv("EMU_HITS_TAB") ? (uint32_t)atoi(getenv("EMU_HITS_TAB")) : (uint32_t)CANDS_TAB;
+  if (hitsTab < 8 || hitsTab > (uint32_t)CANDS_TAB) hitsTab = CANDS_TAB;
   std::vector<uint8_t> hitlds(hits_lds_bytes(hitsW, CANDS_TAB) + 64);
   if (split) { b.hitpool = hitpool.data(); b.hitpool_cap = hitpool.size(); b.hitrun = hitrun.data(); b.hit_count = &hit_count; }
   unsigned long long nwin_strands = 0, nhbm_strands = 0, nsplit_strands = 0;
+  // EMU_DUMP_HITS=<file> (with EMU_SPLIT=1): what stage_hits left behind, in the layout written at the end of main
+  const char *dump_hits = split ? getenv("EMU_DUMP_HITS") : nullptr;
+  std::vector<uint8_t> qmask_hits(dump_hits ? qmask.size() : 1, 0), qmask_seed(dump_hits ? qmask.size() : 1, 0);
   for (uint32_t r = 0; r < n; r++) {
     const uint32_t len = (uint32_t)(off[r + 1] - off[r]);
     if (mincover < 1.01) { p.min_cover = (uint32_t)(mincover * len); if (p.min_cover > len) p.min_cover = len; }
@@ -149,10 +156,12 @@ int main(int argc, char **argv) {
       unsigned long long ph[16] = {0};
       if (split && len <= 255) {
         HitsScratch hx;
-        hx.lds = hitlds.data(); hx.lds_bytes = hitlds.size(); hx.W = hitsW; hx.tab = CANDS_TAB;
+        hx.lds = hitlds.data(); hx.lds_bytes = hitlds.size(); hx.W = hitsW; hx.tab = hitsTab;
         unsigned long long hph[4] = {0, 0, 0, 0};
+        if (dump_hits) memcpy(qmask_seed.data() + (size_t)2 * r * qmax, qmask.data() + (size_t)2 * r * qmax, (size_t)2 * qmax);   // as stage_seed left it
         stage_hits(b, ix, p, r, 0, hx, hph);
         stage_hits(b, ix, p, r, 1, hx, hph);
+        if (dump_hits) memcpy(qmask_hits.data() + (size_t)2 * r * qmax, qmask.data() + (size_t)2 * r * qmax, (size_t)2 * qmax);   // as stage_hits left it
         nsplit_strands += (hitrun[2 * r].mode == HITRUN_SORTED) + (hitrun[2 * r + 1].mode == HITRUN_SORTED);
         stage_cands_v2<false, true>(b, ix, p, r, c2, ph);
       } else if (len > 255) stage_cands_v2<true>(b, ix, p, r, c2, ph);
@@ -205,6 +214,23 @@ int main(int argc, char **argv) {
   if (err_flag) {
     fprintf(stderr, "emu: %d reads with errors\n", err_flag);
     for (uint32_t r = 0; r < n; r++) if (stat[r].err || ch[r].err) fprintf(stderr, "emu: read %u: candidate stage %d, alignment stage %d\n", r, ch[r].err, stat[r].err);
+  }
+  if (dump_hits) {
+    // "SMGHITS1", u32 nstrands, stride, window, tab, u64 hit_count, pool_cap; then per strand u32 n_seeds[], seed_rank[], status[];
+    // SeedRec seeds[nstrands][stride]; u8 qmask[nstrands][stride]; HitRun runs[nstrands]; u64 pool[min(hit_count, pool_cap)];
+    // u8 qmask_seed[nstrands][stride] (the qualifiers before stage_hits: the entry has no such field, a test takes them from a second call)
+    FILE *hf = fopen(dump_hits, "wb");
+    if (!hf) { fprintf(stderr, "emu: cannot write %s\n", dump_hits); return 1; }
+    const uint32_t head[4] = {2 * n, qmax, hitsW, hitsTab};
+    const uint64_t cnt[2] = {hit_count, (uint64_t)hitpool.size()};
+    fwrite("SMGHITS1", 1, 8, hf); fwrite(head, 4, 4, hf); fwrite(cnt, 8, 2, hf);
+    for (int f = 0; f < 3; f++) for (uint32_t rs = 0; rs < 2 * n; rs++) { const uint32_t v = f == 0 ? hi[rs].n_seeds : (f == 1 ? hi[rs].seed_rank : hi[rs].status); fwrite(&v, 4, 1, hf); }
+    fwrite(seeds.data(), sizeof(SeedRec), (size_t)2 * n * qmax, hf);
+    fwrite(qmask_hits.data(), 1, (size_t)2 * n * qmax, hf);
+    fwrite(hitrun.data(), sizeof(HitRun), (size_t)2 * n, hf);
+    fwrite(hitpool.data(), 8, (size_t)(hit_count < hitpool.size() ? hit_count : hitpool.size()), hf);
+    fwrite(qmask_seed.data(), 1, (size_t)2 * n * qmax, hf);
+    if (fclose(hf)) return 1;
   }
   if (getenv("EMU_STATS")) fprintf(stderr, "windowed strands %llu, HBM strands %llu, strands sorted ahead %llu\n", nwin_strands, nhbm_strands, nsplit_strands);
   return 0;

@@ -11,8 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_library_exports_declared_symbols():
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "smalt_amd", "csrc")], check=True)
     hdr = open(os.path.join(ROOT, "include", "smaltgpu.h")).read()
-    declared = sorted(set(re.findall(r"\b(smaltgpu_[a-z_]+)\s*\(", hdr)))
+    declared = sorted(set(re.findall(r"\b(smaltgpu_[a-z0-9_]+)\s*\(", hdr)))
     assert len(declared) >= 15
+    assert "smaltgpu_hits_batch" in declared and "smaltgpu_sort_u64_batch" in declared
     lib = ctypes.CDLL(os.path.join(ROOT, "smalt_amd", "libsmaltgpu.so"))
     for name in declared:
         assert hasattr(lib, name), name

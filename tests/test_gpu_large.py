@@ -2,7 +2,9 @@
 read), including repeat-rich reads that exercise the hit-list allocation-boundary protocol, and
 the torch-built index image against the oracle's builder."""
 import ctypes as C
+import functools
 import os
+import tempfile
 
 import numpy as np
 import pytest
@@ -24,32 +26,53 @@ def _oracle_map_all(oix, reads, par):
     return out
 
 
-@pytest.mark.parametrize("window", [0, 300, -1024], ids=["w-default", "w300", "deferred-cands"])
-def test_repeat_rich_genome_matches_oracle(window, oracle_built, tmp_path, monkeypatch):
-    """window=300 shrinks the LDS window of the candidate stage so that most strands are streamed in
-    several windows and a few fall back to the HBM working set (a hit region larger than the window).
-    -1024: first-pass candidate slots of 1024 hits per strand -- every repeat read overflows its slot and is deferred to the
-    second pass over the few worst-case slots (the path a read with more hits than 4 x the reference's hit-list allocation
-    takes: 1 in 2 M reads of the bench's reference)."""
-    from smalt_amd import api, synth
-    if window > 0:
-        monkeypatch.setenv("SMALTGPU_CANDS_WINDOW", str(window))
-    if window < 0:
-        monkeypatch.setenv("SMALTGPU_CANDS_HCAP", str(-window))
+@functools.lru_cache(maxsize=None)
+def _repeat_rich_workload():
+    """Sequences, reads and the oracle's results of test_repeat_rich_genome_matches_oracle, computed once for all its cases."""
+    from smalt_amd import synth
     ch = synth.make_reference(4, 2_500_000, seed=21, repeat_frac=0.15, n_fam=1, cons_len=300, divergence=0.05)
     reads, _ = synth.make_reads(ch, 1500, 100, seed=22, sub_rate=0.01, indel_read_frac=0.05)
     seqs = [synth.codes_to_ascii(c) for c in ch]
     rb = [synth.codes_to_ascii(r) for r in reads]
     oix0 = ol.build_index(seqs, ["c%d" % i for i in range(4)], 13, 6)
+    with tempfile.TemporaryDirectory() as tmp:
+        pre = os.path.join(tmp, "rep")
+        assert ol.lib().or_index_write(oix0, pre.encode()) == 0
+        oix = ol.lib().or_index_read(pre.encode())
+    exp = _oracle_map_all(oix, rb, ol.default_params(oix))
+    return oix0, rb, exp
+
+
+REPEAT_RICH_CASES = {"w-default": {}, "w300": {"SMALTGPU_CANDS_WINDOW": "300"}, "deferred-cands": {"SMALTGPU_CANDS_HCAP": "1024"},
+                     "fused": {"SMALTGPU_HITS_SPLIT": "0"}, "fused-w300": {"SMALTGPU_HITS_SPLIT": "0", "SMALTGPU_CANDS_WINDOW": "300"},
+                     "hits-w256": {"SMALTGPU_HITS_WINDOW": "256"}}
+
+
+@pytest.mark.parametrize("case", list(REPEAT_RICH_CASES))
+def test_repeat_rich_genome_matches_oracle(case, oracle_built, tmp_path, monkeypatch):
+    """w300 shrinks the LDS window of the candidate stage so that most strands are streamed in
+    several windows and a few fall back to the HBM working set (a hit region larger than the window).
+    deferred-cands: first-pass candidate slots of 1024 hits per strand -- every repeat read overflows its slot and is deferred to the
+    second pass over the few worst-case slots (the path a read with more hits than 4 x the reference's hit-list allocation
+    takes: 1 in 2 M reads of the bench's reference).
+    fused: S3 stays inside the candidate stage of a short-read mapper (SMALTGPU_HITS_SPLIT=0: k_cands with the fused gather, one
+    window or, with w300, windows of ascending diagonal); hits-w256: k_hits gathers in windows of 256 keys (SMALTGPU_HITS_WINDOW)."""
+    from smalt_amd import api
+    for name, value in REPEAT_RICH_CASES[case].items():
+        monkeypatch.setenv(name, value)
+    oix0, rb, exp = _repeat_rich_workload()
     pre = str(tmp_path / "rep")
     assert ol.lib().or_index_write(oix0, pre.encode()) == 0
-    oix = ol.lib().or_index_read(pre.encode())
-    exp = _oracle_map_all(oix, rb, ol.default_params(oix))
     # with 100 bp reads the hit list holds 16384 words (hashhit.c:1266): some repeat reads exceed it
     # and take the allocation-boundary retry protocol (checked on the CPU: 3 of the first 600 reads)
     gix = api.Index.load(pre, 0)
     mp = api.Mapper(gix, len(rb), 100)
     try:
+        if case.startswith("fused"):                        # the mapper really keeps S3 inside k_cands: the stand-alone entry refuses it
+            with pytest.raises(api.SmaltGpuError):
+                mp.hits_batch(rb[:1], None, gix.default_params())
+        if case == "hits-w256":
+            assert mp.hits_batch(rb[:1], None, gix.default_params())["window"] == 256
         res, stats = mp.map_batch(rb, [b"I" * len(r) for r in rb], gix.default_params())
     finally:
         mp.close()
@@ -165,6 +188,47 @@ def test_candidate_pool_overflow_is_recovered(oracle_built, tmp_path):
             finally:
                 mp.close()
     finally:
+        gix.close()
+
+
+def test_hit_pool_overflow_is_recovered(oracle_built, tmp_path, monkeypatch):
+    """The pool of sorted hit keys (k_hits) at its floor of 2^20 keys (SMALTGPU_HITS_PER_READ=64) under a batch whose strands hold
+    at least 1.25 x 2^20 keys by the plain reference (tests/hits_ref.py over the seed tables of smaltgpu_hits_batch), so that some
+    strands overflow whatever the order of the reservations: 152 reads of 100 bases cut from the 900-copy repeat of the
+    test_gpu_hits workload, k=11 s=3 -- the smallest prefix of those reads that meets the condition.  smaltgpu_map_batch must
+    re-map the reads that did not fit and return what the oracle returns, twice through one mapper.  (The oracle maps the 152 reads
+    in 2 s on one CPU core.)"""
+    import hits_ref as hr
+    from smalt_amd import api
+    from test_gpu_hits import workload
+    monkeypatch.setenv("SMALTGPU_HITS_PER_READ", "64")
+    seqs, rb_all = workload()
+    rb = rb_all[200:352]
+    oix0 = ol.build_index(seqs, ["c%d" % i for i in range(len(seqs))], 11, 3)
+    pre = str(tmp_path / "hovf")
+    assert ol.lib().or_index_write(oix0, pre.encode()) == 0
+    oix = ol.lib().or_index_read(pre.encode())
+    exp = _oracle_map_all(oix, rb, ol.default_params(oix))
+    gix = api.Index.load(pre, 0)
+    mp = api.Mapper(gix, len(rb), 100)
+    try:
+        par = gix.default_params()
+        quals = [b"I" * len(r) for r in rb]
+        got = mp.hits_batch(rb, quals, par)
+        assert got["pool_cap"] == 1 << 20
+        runs = hr.expect_batch(hr.HostIndex(oix), par, [len(r) for r in rb], got)
+        total = sum(e.keys.size for e in runs)
+        assert total >= (5 << 20) // 4, total
+        assert got["hit_count"] == total and hr.check_batch(runs, got, True, None, None, overflow=True) >= 1
+        for rep in range(2):                                # the mapper stays usable after a recovery
+            res, stats = mp.map_batch(rb, quals, par)
+            for i in range(len(rb)):
+                assert stats[i]["err"] == 0
+                assert res[i] == exp[i][0], (rep, i)
+                for kk, v in exp[i][1].items():
+                    assert stats[i][kk] == v, (rep, i, kk)
+    finally:
+        mp.close()
         gix.close()
 
 
