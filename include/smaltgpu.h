@@ -651,7 +651,9 @@ int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t 
 
 /* The 64-bit key sorts of the candidate stage, one wave per array (array t in keys[off[t]..off[t+1])): the array is copied to
  * LDS, sorted and copied out.  form 0, 1, 2: the register network over 4, 8, 16 keys per lane (arrays of at most 256, 512,
- * 1024 keys); form 3: the network in LDS (at most 1024 keys).  SMALTGPU_EARG for a longer array. */
+ * 1024 keys); form 3: the network in LDS (at most 1024 keys).  form 4, 5: the sorts of the HBM working set, the network over
+ * global memory and the sort in chunks of 1024 keys (registers inside a chunk, memory across chunks); the array is copied to its
+ * place in out and sorted there, at most 65536 keys.  SMALTGPU_EARG for a longer array. */
 int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out);
 
 const char *smaltgpu_last_error(void);

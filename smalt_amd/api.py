@@ -134,7 +134,7 @@ class HitsOut(C.Structure):            # smaltgpu_hits_out
 
 
 HITRUN_NONE, HITRUN_SORTED, HITRUN_OVERFLOW = 0, 1, 2          # SMALTGPU_HITRUN_*
-SORT_REG4, SORT_REG8, SORT_REG16, SORT_LDS = 0, 1, 2, 3        # forms of smaltgpu_sort_u64_batch
+SORT_REG4, SORT_REG8, SORT_REG16, SORT_LDS, SORT_HBM, SORT_CHUNKED = 0, 1, 2, 3, 4, 5        # forms of smaltgpu_sort_u64_batch
 
 # SMALTGPU_BAND_*: the forms of the K3 band pass (smaltgpu_band_align_nodes)
 BAND_ROWS, BAND_ANTIDIAG, BAND_WAVE2, BAND_WAVE4, BAND_WAVE7, BAND_WAVE12, BAND_STRIP8, BAND_STRIP16, BAND_SCALAR = range(9)
@@ -741,13 +741,18 @@ class Mapper:
 
     def sort_u64_batch(self, arrays, form: int):
         """Stand-alone 64-bit key sorts (smaltgpu_sort_u64_batch): list of uint64 numpy arrays -> list of sorted arrays.
-        form: SORT_REG4 / SORT_REG8 / SORT_REG16 (register network, at most 256 / 512 / 1024 keys) or SORT_LDS."""
+        form: SORT_REG4 / SORT_REG8 / SORT_REG16 (register network, at most 256 / 512 / 1024 keys), SORT_LDS (the network in
+        LDS, at most 1024 keys), SORT_HBM / SORT_CHUNKED (the network over global memory / the sort in chunks of 1024 keys, in
+        place on global memory, at most 65536 keys).  A guard array of equal keys goes in behind the last array (no sort moves
+        equal keys) and must come back as it went in: a store past the end of an array shows there."""
         import numpy as np
-        off = np.zeros(len(arrays) + 1, dtype=np.uint32)
-        off[1:] = np.cumsum([len(a) for a in arrays])
-        keys = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros(0), dtype=np.uint64)
-        if keys.size == 0:
-            keys = np.zeros(1, dtype=np.uint64)
+        guard = np.full(64, 0xA5C3A5C3A5C3A5C3, dtype=np.uint64)
+        arrays = [np.ascontiguousarray(a, dtype=np.uint64) for a in arrays]
+        off = np.zeros(len(arrays) + 2, dtype=np.uint32)
+        off[1:] = np.cumsum([len(a) for a in arrays] + [guard.size])
+        keys = np.concatenate(arrays + [guard])
         out = np.zeros(keys.size, dtype=np.uint64)
-        _check(lib().smaltgpu_sort_u64_batch(self.h, keys.ctypes.data, off.ctypes.data, len(arrays), form, out.ctypes.data))
+        _check(lib().smaltgpu_sort_u64_batch(self.h, keys.ctypes.data, off.ctypes.data, len(arrays) + 1, form, out.ctypes.data))
+        if not np.array_equal(out[off[-2]:], guard):
+            raise SmaltGpuError(EINTERNAL, "smaltgpu_sort_u64_batch: the guard behind the last array was written")
         return [out[off[t]:off[t + 1]] for t in range(len(arrays))]

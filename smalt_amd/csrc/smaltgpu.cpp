@@ -1551,8 +1551,8 @@ extern "C" int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, con
 
 extern "C" int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out) {
   if (!m || !keys || !off || !out) return fail(SMALTGPU_EARG, "null argument");
-  if (form < 0 || form > 3) return fail(SMALTGPU_EARG, "unknown form %d", form);
-  const uint32_t nmax = form == 0 ? 256u : (form == 1 ? 512u : 1024u);
+  if (form < 0 || form > 5) return fail(SMALTGPU_EARG, "unknown form %d", form);
+  const uint32_t nmax = form == 0 ? 256u : (form == 1 ? 512u : (form <= 3 ? 1024u : 65536u));
   for (uint32_t t = 0; t < narr; t++) if (off[t + 1] < off[t] || off[t + 1] - off[t] > nmax) return fail(SMALTGPU_EARG, "array %u does not fit form %d (at most %u keys)", t, form, nmax);
   HIPCHK(hipSetDevice(m->device));
   const size_t tot = narr ? off[narr] : 0;
@@ -1563,7 +1563,7 @@ extern "C" int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys,
   if (!rv) {
     if (tot) (void)hipMemcpy(dk, keys, tot * 8, hipMemcpyHostToDevice);
     (void)hipMemcpy(doff, off, ((size_t)narr + 1) * 4, hipMemcpyHostToDevice);
-    if (launch_sort_u64_raw(m->stream, dk, doff, narr, form, dout)) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
+    if (form >= 4 ? launch_sort_u64_hbm_raw(m->stream, dk, doff, narr, form, dout) : launch_sort_u64_raw(m->stream, dk, doff, narr, form, dout)) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
     else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
     else if (tot) (void)hipMemcpy(out, dout, tot * 8, hipMemcpyDeviceToHost);
   }

@@ -62,7 +62,10 @@ int sw16_rowframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, 
 int sw16_pairframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols);
 int launch_rank_sort_raw(hipStream_t s, const uint32_t *keys, const uint32_t *off, uint32_t narr, int nneed, int in_lds, uint32_t *kv,
                          uint32_t *out_key, uint32_t *out_idx);
-// test entry of the 64-bit key sorts: form 0/1/2 = wave_sort_u64_reg<4|8|16>, 3 = wave_sort_u64; every array at most 1024 keys
+// test entry of the 64-bit key sorts: form 0/1/2 = wave_sort_u64_reg<4|8|16>, 3 = wave_sort_u64; every array at most 1024 keys (in LDS)
 int launch_sort_u64_raw(hipStream_t s, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out);
+// ... and of the sorts of the HBM working set, in place on global memory (in `out`), any length: form 4 = wave_sort_u64,
+// 5 = wave_sort_u64_chunked (smg_sortraw.hip: a translation unit of its own, see there)
+int launch_sort_u64_hbm_raw(hipStream_t s, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out);
 
 }  // namespace smg

@@ -1,5 +1,6 @@
 """S3 on its own (kernel k_hits, smaltgpu_hits_batch) and the 64-bit wave sorts (smaltgpu_sort_u64_batch) against plain
-references: tests/hits_ref.py for the hit runs (exact integer equality, key by key), np.sort for the sorts.  Every case first
+references: tests/hits_ref.py for the hit runs (exact integer equality, key by key), np.sort for the sorts (in LDS up to 1024 keys,
+and the two sorts of the HBM working set in place on global memory up to 65 536 keys).  Every case first
 asserts, from the reference alone, that the batch holds the strands the case is about -- and that no eligible strand was left
 to the candidate stage (HITRUN_NONE), which end-to-end parity cannot see: k_cands would quietly gather that strand again."""
 import functools
@@ -375,6 +376,79 @@ def test_wave_sorts_equal_numpy(sort_mapper, form):
 
 def test_sort_refuses_an_array_above_the_form(sort_mapper):
     from smalt_amd import api
-    for form, n in ((0, 257), (1, 513), (2, 1025), (3, 1025), (4, 1)):
+    for form, n in ((0, 257), (1, 513), (2, 1025), (3, 1025), (4, 65537), (5, 65537), (6, 1), (-1, 1)):
         with pytest.raises(api.SmaltGpuError):
             sort_mapper.sort_u64_batch([np.zeros(n, dtype=np.uint64)], form)
+
+
+# The sorts of the HBM working set, in place on global memory (forms 4 and 5: wave_sort_u64, wave_sort_u64_chunked).  Lengths
+# around the wave, the 256-key threshold and every chunk count at which the chunked sort changes shape: n - 1 keys leave the last
+# chunk partial (and, at 2^m + 1024 c - 1, the mirror step with partners beyond n), n + 1 adds a chunk of one key and at a power
+# of two doubles the padded size; above 2048 keys the half-cleaners that span chunks (j >= 1024) run, at 3072 and 12288 the
+# padded size is not the array's.
+HBM_SORT_LENGTHS = ([0, 1, 2, 63, 64, 65, 255, 256, 257] + [n + d for n in (1024, 2048, 3072, 4096, 8192, 12288, 16384, 32768) for d in (-1, 0, 1)]
+                    + [1500, 5000, 40000, 65535, 65536])
+# form -> lengths: the network in memory pays a round trip per stage, so it takes the lengths up to 16385 and one full array
+HBM_SORT_FORMS = {4: [n for n in HBM_SORT_LENGTHS if n <= 16385] + [65536], 5: HBM_SORT_LENGTHS}
+HBM_SORT_PATTERNS = ["rnd63", "rnd64", "8values", "sorted", "reversed", "organpipe", "constant", "chunks-sorted"]
+
+
+def _hbm_sort_array(pattern, n, rng):
+    if pattern == "rnd63":
+        return rng.integers(0, 1 << 63, size=n, dtype=np.uint64)
+    if pattern == "rnd64":                                    # up to 2^64 - 2: the register forms pad with ~0
+        return rng.integers(0, 0xFFFFFFFFFFFFFFFF, size=n, dtype=np.uint64)
+    if pattern == "8values":
+        return rng.integers(0, 1 << 63, size=8, dtype=np.uint64)[rng.integers(0, 8, size=n)]
+    if pattern == "constant":
+        return np.full(n, 0x0123456789ABCDEF, dtype=np.uint64)
+    a = np.sort(rng.integers(0, 1 << 63, size=n, dtype=np.uint64))
+    if pattern == "reversed":
+        return a[::-1].copy()
+    if pattern == "organpipe":
+        return np.concatenate([a[::2], a[1::2][::-1]])
+    if pattern == "chunks-sorted":                            # every chunk of 1024 keys in order on its own
+        a = rng.permutation(a)
+        return np.concatenate([np.sort(a[o:o + 1024]) for o in range(0, n, 1024)] or [a])
+    assert pattern == "sorted"
+    return a
+
+
+@pytest.mark.parametrize("form", [4, 5], ids=["hbm", "chunked"])
+def test_hbm_sorts_equal_numpy(sort_mapper, form):
+    """Every length of the form's list in eight contents, one wave per array, all arrays in one launch; exact equality with
+    np.sort, and the guard behind the last array (the wrapper's) comes back untouched."""
+    from smalt_amd import api
+    assert (api.SORT_HBM, api.SORT_CHUNKED) == (4, 5)
+    rng = np.random.default_rng(95 + form)
+    cases = [(p, n) for n in HBM_SORT_FORMS[form] for p in HBM_SORT_PATTERNS]
+    arrays = [_hbm_sort_array(p, n, rng) for p, n in cases]
+    assert all(a.size == n and a.dtype == np.uint64 for a, (_, n) in zip(arrays, cases))
+    out = sort_mapper.sort_u64_batch(arrays, form)
+    assert len(out) == len(arrays)
+    for (p, n), a, o in zip(cases, arrays, out):
+        assert np.array_equal(o, np.sort(a)), (form, p, n)
+
+
+def test_hbm_sorts_on_runs_of_the_workload(ctx, sort_mapper):
+    """Production-shaped input: what the candidate stage sorts is a concatenation of ascending position lists (one per seed).  The
+    lists of the workload's strands (hits_ref, which takes them from the index), strand after strand, cut into arrays of every
+    length of the forms' lists; both forms."""
+    par = _params(ctx.gix, "seqbyseq")
+    _, exp = _run(ctx, par)
+    lists = [l for e in exp if e.mode == hr.HITRUN_SORTED for l in e.lists]
+    assert all(l.size < 2 or bool((l[1:] > l[:-1]).all()) for l in lists)
+    stream = np.concatenate(lists)
+    assert stream.size > 100_000 and len(lists) > 1000
+    for form, lengths in HBM_SORT_FORMS.items():
+        arrays, at = [], 0
+        for n in lengths:
+            if at + n > stream.size:
+                at = (at + n) % 997                       # start over, off the earlier cuts
+            arrays.append(stream[at:at + n].copy())
+            at += n
+        assert [a.size for a in arrays] == lengths
+        assert all(np.count_nonzero(a[1:] < a[:-1]) >= 4 for a in arrays if a.size > 4096)       # several lists each
+        out = sort_mapper.sort_u64_batch(arrays, form)
+        for a, o in zip(arrays, out):
+            assert np.array_equal(o, np.sort(a)), (form, a.size)

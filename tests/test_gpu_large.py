@@ -50,8 +50,11 @@ REPEAT_RICH_CASES = {"w-default": {}, "w300": {"SMALTGPU_CANDS_WINDOW": "300"}, 
 
 @pytest.mark.parametrize("case", list(REPEAT_RICH_CASES))
 def test_repeat_rich_genome_matches_oracle(case, oracle_built, tmp_path, monkeypatch):
-    """w300 shrinks the LDS window of the candidate stage so that most strands are streamed in
-    several windows and a few fall back to the HBM working set (a hit region larger than the window).
+    """w300 shrinks the LDS window of the candidate stage so that the repeat strands are streamed in several windows.  None of them
+    falls back to the HBM working set for a hit region larger than the window, as this text once claimed: the regions of a
+    300-base family hold a few hundred keys at most (the kernel and the one-lane host build both count 1 strand of the 3000 on
+    the HBM working set, in every case here: the one the allocation-boundary protocol sends there; work[22] is printed below).  The
+    fall back and its roll-back are pinned by the tandem cases of tests/test_gpu_cands.py.
     deferred-cands: first-pass candidate slots of 1024 hits per strand -- every repeat read overflows its slot and is deferred to the
     second pass over the few worst-case slots (the path a read with more hits than 4 x the reference's hit-list allocation
     takes: 1 in 2 M reads of the bench's reference).
@@ -74,6 +77,7 @@ def test_repeat_rich_genome_matches_oracle(case, oracle_built, tmp_path, monkeyp
         if case == "hits-w256":
             assert mp.hits_batch(rb[:1], None, gix.default_params())["window"] == 256
         res, stats = mp.map_batch(rb, [b"I" * len(r) for r in rb], gix.default_params())
+        print(case, "strands on the HBM working set (work[22]):", mp.timers()[1][22])
     finally:
         mp.close()
         gix.close()
