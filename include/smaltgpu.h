@@ -649,6 +649,27 @@ typedef struct smaltgpu_hits_out {
 int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
                         const smaltgpu_params *par, uint32_t window, uint64_t pool_keys, smaltgpu_hits_out *out);
 
+/* The on-the-fly index of the rescue round on its own (kernel k_fine_index): the intervals of nreads reads go up as in a call of
+ * smaltgpu_map_batch_ctx with fine_index set, the mapper's position buffer (with one word behind the last read's slice) and
+ * index rows are filled with `guard`, the kernel runs on `grid` workgroups (0 = one per read, as in a mapping call) and the
+ * buffers come back in host copies owned by the mapper, valid until its next call of this function.  Read r owns
+ * idx[r * idx_stride .. + nkeys] (first position of every key's list, idx[nkeys] = words indexed) and
+ * pos[fine_off[r] .. fine_off[r + 1]): the slice is sized for every word of the windows, so its tail behind idx[nkeys] is
+ * unused where words hold non-standard bases. */
+typedef struct smaltgpu_fine_out {
+  uint32_t nreads, idx_stride, nkeys;
+  uint64_t npos;                     /* words of pos: fine_off[nreads] + 1 */
+  const uint32_t *fine_off;          /* [nreads + 1] */
+  const uint32_t *idx;               /* [nreads][idx_stride] */
+  const uint32_t *pos;               /* [npos] */
+} smaltgpu_fine_out;
+int smaltgpu_fine_index_batch(smaltgpu_mapper *m, uint32_t nreads, const uint64_t *iv_off, const smaltgpu_interval *iv, uint32_t grid,
+                              uint32_t guard, smaltgpu_fine_out *out);
+/* Scratch geometry of the candidate stage (read-only, for tests that predict its branches): first-pass hits per strand,
+ * candidate capacity and bytes of the LDS working set when S3 runs inside the stage; the same three of the second pass (0: the
+ * mapper has one pass); the stride of read offsets; the most intervals a read of a restricted call may have. */
+int smaltgpu_cands_geometry(smaltgpu_mapper *m, uint32_t out[8]);
+
 /* The 64-bit key sorts of the candidate stage, one wave per array (array t in keys[off[t]..off[t+1])): the array is copied to
  * LDS, sorted and copied out.  form 0, 1, 2: the register network over 4, 8, 16 keys per lane (arrays of at most 256, 512,
  * 1024 keys); form 3: the network in LDS (at most 1024 keys).  form 4, 5: the sorts of the HBM working set, the network over

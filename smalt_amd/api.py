@@ -133,7 +133,12 @@ class HitsOut(C.Structure):            # smaltgpu_hits_out
                 ("hit_count", C.c_uint64), ("pool_cap", C.c_uint64), ("pool", C.c_void_p)]
 
 
-HITRUN_NONE, HITRUN_SORTED, HITRUN_OVERFLOW = 0, 1, 2          # SMALTGPU_HITRUN_*
+class FineOut(C.Structure):            # smaltgpu_fine_out
+    _fields_ = [("nreads", C.c_uint32), ("idx_stride", C.c_uint32), ("nkeys", C.c_uint32), ("npos", C.c_uint64),
+                ("fine_off", C.c_void_p), ("idx", C.c_void_p), ("pos", C.c_void_p)]
+
+
+HITRUN_NONE, HITRUN_SORTED, HITRUN_OVERFLOW = 0, 1, 2         # SMALTGPU_HITRUN_*
 SORT_REG4, SORT_REG8, SORT_REG16, SORT_LDS, SORT_HBM, SORT_CHUNKED = 0, 1, 2, 3, 4, 5        # forms of smaltgpu_sort_u64_batch
 
 # SMALTGPU_BAND_*: the forms of the K3 band pass (smaltgpu_band_align_nodes)
@@ -249,6 +254,8 @@ def lib():
         L.smaltgpu_rank_sort_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.smaltgpu_hits_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.c_uint32, C.c_uint64,
                                           C.POINTER(HitsOut)]
+        L.smaltgpu_fine_index_batch.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(Interval), C.c_uint32, C.c_uint32, C.POINTER(FineOut)]
+        L.smaltgpu_cands_geometry.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.smaltgpu_sort_u64_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.smaltgpu_sample_interval.argtypes = [C.c_uint64, C.c_int]
         L.smaltgpu_inshist_from_sample.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_uint64]
@@ -539,11 +546,11 @@ class Mapper:
         return self._unpack(out)
 
     def map_batch_ctx(self, reads: Sequence[bytes], quals: Optional[Sequence[bytes]], params: Params, intervals=None, min_swatscor=None,
-                      prev_max=None, fine_index: bool = False, raw_alignments: bool = False, seed_range=None):
+                      prev_max=None, fine_index: bool = False, raw_alignments: bool = False, seed_range=None, allow_read_errors: bool = False):
         """One round of rmapPair over a batch (smaltgpu_map_batch_ctx): intervals = per read a list of (sidx, lo, hi) or None
         for no restriction at all; min_swatscor = per-read thresholds; prev_max = per read (max, 2ndmax) of the ResultSet
         the call appends to; fine_index = seed against the on-the-fly k=5 index of the intervals; seed_range = per read the
-        (first, last) base its k-mer words come from (the second call of a split read).
+        (first, last) base its k-mer words come from (the second call of a split read); allow_read_errors as in map_batch.
         -> (results, stats, cand_first flags per result)"""
         bases, q, off = self._pack(reads, quals)
         n = len(reads)
@@ -575,7 +582,9 @@ class Mapper:
         ctx.fine_index = 1 if fine_index else 0
         ctx.raw_alignments = 1 if raw_alignments else 0
         out = BatchOut()
-        _check(lib().smaltgpu_map_batch_ctx(self.h, bases, q, off, n, C.byref(params), C.byref(ctx), C.byref(out)))
+        rv = lib().smaltgpu_map_batch_ctx(self.h, bases, q, off, n, C.byref(params), C.byref(ctx), C.byref(out))
+        if rv != 0 and not (allow_read_errors and rv in (ECAP, EINTERNAL, ESCORE, ECPLX) and out.nreads == n):
+            _check(rv)
         res, stats = self._unpack(out)
         cf = [[bool(out.res[j].reverse & 2) for j in range(out.res_off[i], out.res_off[i + 1])] for i in range(n)]
         return res, stats, cf
@@ -738,6 +747,35 @@ class Mapper:
                     run_off=runs["off"].copy(), run_n=runs["n"].copy(), run_mode=runs["mode"].copy(), hit_count=int(out.hit_count),
                     pool_cap=int(out.pool_cap), pool=arr(out.pool, np.uint64, min(int(out.hit_count), int(out.pool_cap))),
                     window=int(out.window), tab=int(out.tab), stride=int(stride))
+
+    def fine_index_batch(self, intervals, grid: int = 0, guard: int = 0xA5C3E187):
+        """Stand-alone k_fine_index (smaltgpu_fine_index_batch): intervals = per read a list of (sidx, lo, hi).  The position buffer
+        and the index rows are filled with `guard` before the kernel runs on `grid` workgroups (0 = one per read).
+        -> dict of numpy copies: fine_off [n + 1], idx [n][idx_stride], pos [fine_off[n] + 1] (one word behind the last slice),
+        nkeys."""
+        import numpy as np
+        n = len(intervals)
+        ivo = (C.c_uint64 * (n + 1))()
+        flat = [iv for lst in intervals for iv in lst]
+        t = 0
+        for i, lst in enumerate(intervals):
+            ivo[i] = t
+            t += len(lst)
+        ivo[n] = t
+        arr = (Interval * max(1, len(flat)))(*[Interval(a, b, c) for a, b, c in flat])
+        out = FineOut()
+        _check(lib().smaltgpu_fine_index_batch(self.h, n, ivo, arr, grid, guard, C.byref(out)))
+
+        def take(ptr, count):
+            return np.frombuffer(C.string_at(ptr, count * 4), dtype=np.uint32).copy() if count else np.zeros(0, dtype=np.uint32)
+        return dict(fine_off=take(out.fine_off, n + 1), idx=take(out.idx, n * out.idx_stride).reshape(n, out.idx_stride),
+                    pos=take(out.pos, int(out.npos)), nkeys=int(out.nkeys), guard=guard)
+
+    def cands_geometry(self):
+        """Scratch geometry of the candidate stage (smaltgpu_cands_geometry) -> dict; the pass-2 entries are 0 for a mapper with one pass."""
+        g = (C.c_uint32 * 8)()
+        _check(lib().smaltgpu_cands_geometry(self.h, g))
+        return dict(hcap_strand=g[0], candcap=g[1], lds_bytes=g[2], hcap_strand2=g[3], candcap2=g[4], lds_bytes2=g[5], qmax=g[6], iv_max=g[7])
 
     def sort_u64_batch(self, arrays, form: int):
         """Stand-alone 64-bit key sorts (smaltgpu_sort_u64_batch): list of uint64 numpy arrays -> list of sorted arrays.

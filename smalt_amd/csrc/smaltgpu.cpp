@@ -432,7 +432,7 @@ struct smaltgpu_mapper {
   bool history = false;                      // serial-order mode (smaltgpu_mapper_set_history)
   uint32_t hist_longest = 0;                 // longest read of length >= k of the run so far
   std::vector<uint32_t> h_alloclen;
-  std::vector<uint32_t> h_ivoff, h_fineoff;
+  std::vector<uint32_t> h_ivoff, h_fineoff, h_finepos, h_fineidx;      // (the last two: host copies for smaltgpu_fine_index_batch, test entry)
   std::vector<HitInfoHdr> h_hi;
   bool last_fine = false;
   uint64_t remap_batches = 0;               // device batches smaltgpu_map_batch ran to recover from pool overflows (diagnostic)
@@ -1546,6 +1546,46 @@ extern "C" int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, con
   out->n_seeds = h.n_seeds.data(); out->seed_rank = h.seed_rank.data(); out->status = h.status.data();
   out->seeds = (const smaltgpu_hit_seed *)h.seeds.data(); out->qmask = h.qmask.data(); out->runs = (const smaltgpu_hit_run *)h.runs.data();
   out->hit_count = count; out->pool_cap = cap; out->pool = h.pool.data();
+  return SMALTGPU_OK;
+}
+
+// k_fine_index on its own: the context of a fine round goes up as for a mapping call (upload_ctx), the position buffer and the
+// index rows are filled with a guard pattern, launch_fine_index runs on the mapper's buffers, and everything comes back
+extern "C" int smaltgpu_fine_index_batch(smaltgpu_mapper *m, uint32_t nreads, const uint64_t *iv_off, const smaltgpu_interval *iv, uint32_t grid,
+                                         uint32_t guard, smaltgpu_fine_out *out) {
+  if (!m || !iv_off || !out) return fail(SMALTGPU_EARG, "null argument");
+  if (nreads > m->max_reads) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity");
+  HIPCHK(hipSetDevice(m->device));
+  smaltgpu_callctx ctx;
+  memset(&ctx, 0, sizeof(ctx));
+  ctx.iv_off = iv_off; ctx.iv = iv; ctx.fine_index = 1;
+  CtxDev cd;
+  int rv = upload_ctx(m, &ctx, nreads, &cd);
+  if (rv) return rv;
+  hipStream_t s = m->stream;
+  const size_t npos = (size_t)m->h_fineoff[nreads] + 1, nidx = (size_t)nreads * FINE_IDX_STRIDE;      // (one word behind the last slice)
+  std::vector<uint32_t> &hp = m->h_finepos, &hi = m->h_fineidx;
+  hp.assign(npos, guard); hi.assign(nidx ? nidx : 1, guard);
+  HIPCHK(hipMemcpyAsync(cd.fine_pos, hp.data(), npos * 4, hipMemcpyHostToDevice, s));
+  if (nidx) HIPCHK(hipMemcpyAsync(cd.fine_idx, hi.data(), nidx * 4, hipMemcpyHostToDevice, s));
+  Batch b = m->b;
+  b.nreads = nreads; b.iv_off = cd.iv_off; b.iv = cd.iv; b.fine_idx = cd.fine_idx; b.fine_pos = cd.fine_pos; b.fine_off = cd.fine_off;
+  rv = launch_fine_index(s, b, m->ix->d, grid);
+  if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(hp.data(), cd.fine_pos, npos * 4, hipMemcpyDeviceToHost));
+  if (nidx) HIPCHK(hipMemcpy(hi.data(), cd.fine_idx, nidx * 4, hipMemcpyDeviceToHost));
+  out->nreads = nreads; out->idx_stride = FINE_IDX_STRIDE; out->nkeys = FINE_NKEYS; out->npos = (uint64_t)npos;
+  out->fine_off = m->h_fineoff.data(); out->idx = hi.data(); out->pos = hp.data();
+  return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_cands_geometry(smaltgpu_mapper *m, uint32_t out[8]) {
+  if (!m || !out) return fail(SMALTGPU_EARG, "null argument");
+  const bool two = m->cand_scr2 != nullptr;
+  out[0] = m->cg.hcap_strand; out[1] = m->cg.candcap; out[2] = cands_lds_bytes(m->cg);
+  out[3] = two ? m->cg2.hcap_strand : 0u; out[4] = two ? m->cg2.candcap : 0u; out[5] = two ? cands_lds_bytes(m->cg2) : 0u;
+  out[6] = m->qmax; out[7] = (uint32_t)IV_MAX;
   return SMALTGPU_OK;
 }
 

@@ -12,7 +12,9 @@ enum : int { SW_FULL_WMAX = 1016,   // longest reference window of the register-
 int launch_encode(hipStream_t s, const uint8_t *bases, const uint64_t *off, uint32_t n, uint8_t *codes, uint8_t *codes_rc);
 int launch_gather_reads(hipStream_t s, uint8_t *dst_bases, uint8_t *dst_quals, const uint64_t *dst_off, uint32_t n, const uint32_t *ids,
                         const uint8_t *const src_bases[2], const uint8_t *const src_quals[2], const uint64_t *const src_off[2]);
-int launch_fine_index(hipStream_t s, const Batch &b, const DevIndex &ix);     // needs b.iv_off/iv, b.fine_idx/fine_pos/fine_off
+// needs b.iv_off/iv, b.fine_idx/fine_pos/fine_off; grid: workgroups (test hook), 0 = one per read up to 65535
+int launch_fine_index(hipStream_t s, const Batch &b, const DevIndex &ix, uint32_t grid = 0);
+inline uint32_t fine_index_grid(uint32_t nreads, uint32_t grid) { const uint32_t g = grid && grid < 65535u ? grid : 65535u; return nreads < g ? nreads : g; }
 int launch_seed(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, size_t sbytes, uint32_t nslots);
 struct CandGeom {              // scratch geometry of the candidate stage (both code paths share one HBM slot)
   uint32_t hcap;               // hits of both strands, power of two (sequential path)
@@ -29,6 +31,8 @@ inline size_t cand_slot_bytes(const CandGeom &g, uint32_t qmax, int s) {
   size_t b = cands_v2_hbm_bytes(qmax, s, g.hcap_strand, g.ngrp, g.candcap, true);
   return a > b ? a : b;
 }
+// LDS working set of the candidate stage when S3 runs inside it (k_cands<false>, k_cands<true>): hits and per-list tables
+inline uint32_t cands_lds_bytes(const CandGeom &g) { return (uint32_t)(((strand_work_bytes<uint16_t>(g.lds_hits) + 15) & ~(size_t)15) + (size_t)5 * g.tab * 4); }
 int launch_hits(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t W, uint32_t tab, uint32_t nwg);
 int launch_cands(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, uint32_t nslots, const CandGeom &g);
 int launch_replay(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p);

@@ -126,9 +126,9 @@ __global__ void __launch_bounds__(64) k_fine_index(Batch b, DevIndex ix) {
   }
 }
 
-int launch_fine_index(hipStream_t s, const Batch &b, const DevIndex &ix) {
+int launch_fine_index(hipStream_t s, const Batch &b, const DevIndex &ix, uint32_t grid) {
   if (!b.nreads) return 0;
-  hipLaunchKernelGGL(k_fine_index, dim3(b.nreads < 65535u ? b.nreads : 65535u), dim3(64), 0, s, b, ix);
+  hipLaunchKernelGGL(k_fine_index, dim3(fine_index_grid(b.nreads, grid)), dim3(64), 0, s, b, ix);
   return (int)hipGetLastError();
 }
 
@@ -1832,7 +1832,7 @@ int launch_hits(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar 
 int launch_cands(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, uint32_t nslots, const CandGeom &g) {
   if (!b.nreads) return 0;
   uint32_t grid = b.nreads < nslots ? b.nreads : nslots;
-  const uint32_t lds_bytes = (uint32_t)(((strand_work_bytes<uint16_t>(g.lds_hits) + 15) & ~(size_t)15) + (size_t)5 * g.tab * 4);
+  const uint32_t lds_bytes = cands_lds_bytes(g);
   const size_t seq_bytes = (ix.nseq > 0 && ix.nseq < 512) ? (((size_t)ix.nseq + 1) * 4 + 15) & ~(size_t)15 : 0;     // LDS copy of seqlo
   if (b.qmax > 255) hipLaunchKernelGGL(k_cands<true>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, scratch, g, lds_bytes);
   else if (b.hitrun) {

@@ -112,9 +112,41 @@ int main(int argc, char **argv) {
   b.work = workctr; b.long_list = nullptr; b.long_cap = 0; b.strip_list = nullptr; b.strip_cap = 0; b.tile_qmax = 512;
 
   std::vector<uint8_t> sscr(seed_scratch_bytes(qmax, ix.s));
-  const uint32_t hcap = 1u << 16, segcap = 1u << 15, candcap = 1u << 16;
+  // EMU_INTERVALS=<file>: every read is one of rmapPair's restricted calls over the main index (rmap.c:438-492); line r of the
+  // file holds the search intervals of read r as `sx lo hi` triples (0-based, inclusive; an empty line: no interval, no seeds).
+  // EMU_CANDCAP / EMU_LDS_BYTES: candidates per slot and bytes of the block that stands for LDS (restricted calls keep the
+  // counts of every (seed, interval) pair there, or behind the ranking arrays, or take them interval by interval)
+  std::vector<uint32_t> iv_off;
+  std::vector<IvRec> ivs;
+  if (const char *ivf = getenv("EMU_INTERVALS")) {
+    FILE *f = fopen(ivf, "r");
+    if (!f) { fprintf(stderr, "emu: cannot read %s\n", ivf); return 1; }
+    char *ln = nullptr; size_t lc = 0;
+    iv_off.push_back(0);
+    while (iv_off.size() <= n && getline(&ln, &lc, f) > 0) {
+      char *q = ln, *e;
+      for (;;) {
+        const long sxv = strtol(q, &e, 10); if (e == q) break; q = e;
+        const unsigned long lo = strtoul(q, &e, 10); if (e == q) { fprintf(stderr, "emu: bad interval line\n"); return 1; } q = e;
+        const unsigned long hiv = strtoul(q, &e, 10); if (e == q) { fprintf(stderr, "emu: bad interval line\n"); return 1; } q = e;
+        if (sxv < 0 || sxv >= (long)hix.nseq || hiv < lo || hix.sop[(size_t)sxv] + hiv >= hix.sop[(size_t)sxv + 1]) { fprintf(stderr, "emu: interval outside its sequence\n"); return 1; }
+        IvRec v; v.sx = (int32_t)sxv; v.lo = (uint32_t)lo; v.hi = (uint32_t)hiv;
+        ivs.push_back(v);
+      }
+      iv_off.push_back((uint32_t)ivs.size());
+    }
+    free(ln); fclose(f);
+    if (iv_off.size() != (size_t)n + 1) { fprintf(stderr, "emu: %s holds %zu lines for %u reads\n", ivf, iv_off.size() - 1, n); return 1; }
+    if (ivs.empty()) ivs.resize(1);
+    b.iv_off = iv_off.data(); b.iv = ivs.data();
+  }
+  const bool restricted = b.iv_off != nullptr;
+  const uint32_t hcap = 1u << 16, segcap = 1u << 15, candcap = restricted && getenv("EMU_CANDCAP") ? (uint32_t)atoi(getenv("EMU_CANDCAP")) : 1u << 16;
   const uint32_t hcap_strand = hcap / 2;
-  std::vector<uint8_t> ldsmem(((strand_work_bytes<uint16_t>(CANDS_LDS_HITS) + 15) & ~(size_t)15) + CANDS_TAB_BYTES);   // stands for the workgroup's LDS block
+  size_t lds_size = ((strand_work_bytes<uint16_t>(CANDS_LDS_HITS) + 15) & ~(size_t)15) + CANDS_TAB_BYTES;
+  if (restricted && getenv("EMU_LDS_BYTES")) lds_size = (size_t)atol(getenv("EMU_LDS_BYTES"));
+  std::vector<uint8_t> ldsmem(lds_size);   // stands for the workgroup's LDS block
+  if (restricted && getenv("EMU_STATS")) fprintf(stderr, "restricted: candcap %u, hcap_strand %u, lds_bytes %zu\n", candcap, hcap_strand, lds_size);
   const uint32_t window = getenv("EMU_WINDOW") ? (uint32_t)atoi(getenv("EMU_WINDOW")) : 0;   // hits per window of the candidate stage
   const char *force = getenv("EMU_CANDS");       // "v1": sequential restatement only; default: as the kernel chooses
   size_t cbytes = cand_scratch_bytes(qmax, ix.s, hcap, ngrp, segcap, candcap);
@@ -150,11 +182,11 @@ int main(int argc, char **argv) {
     SeedScratch sx = seed_scratch_carve(sscr.data(), qmax, ix.s);
     stage_seed(b, ix, p, r, 0, sx);
     stage_seed(b, ix, p, r, 1, sx);
-    if (cands_v2_applicable(p, ix.k, ix.s, len, false) && !(force && !strcmp(force, "v1"))) {
+    if (cands_v2_applicable(p, ix.k, ix.s, len, restricted) && (restricted || !(force && !strcmp(force, "v1")))) {
       CandsV2Scratch c2 = cands_v2_carve(ldsmem.data(), ldsmem.size(), cscr.data() + cbytes * r, qmax, ix.s, hcap_strand, ngrp, candcap, true);
       c2.window = window;
       unsigned long long ph[16] = {0};
-      if (split && len <= 255) {
+      if (split && len <= 255 && !restricted) {
         HitsScratch hx;
         hx.lds = hitlds.data(); hx.lds_bytes = hitlds.size(); hx.W = hitsW; hx.tab = hitsTab;
         unsigned long long hph[4] = {0, 0, 0, 0};
@@ -203,7 +235,7 @@ int main(int argc, char **argv) {
     for (int st = 0; st < 2; st++) { v.hi[st] = hi[2 * r + st]; v.seeds[st] = seeds.data() + (size_t)(2 * r + st) * qmax; v.qmask[st] = qmask.data() + (size_t)(2 * r + st) * qmax; }
     v.ch = ch[r]; v.rc = rcpool.data() + ch[r].rc_off;
     v.ctl = ctl[r]; v.st = stat[r]; v.res = respool.data() + stat[r].res_off; v.dstr = dstrpool.data() + stat[r].dstr_off; v.ngrp = ngrp;
-    if (cands_v2_applicable(p, ix.k, ix.s, v.qlen, false) && !(force && !strcmp(force, "v1"))) {
+    if (cands_v2_applicable(p, ix.k, ix.s, v.qlen, restricted) && (restricted || !(force && !strcmp(force, "v1")))) {
       CandsV2Scratch c2 = cands_v2_carve(nullptr, 0, cscr.data() + cbytes * r, qmax, ix.s, hcap_strand, ngrp, candcap, true);
       cands_v2_records(crec, c2, v.ch.ncand <= candcap ? v.ch.ncand : 0, v.qlen > 255); v.cand = crec.data(); v.sort_idx = c2.sort_idx; v.sort_keys = c2.sort_keys; v.hitwords = c2.dbg_words; v.grp_first = c2.dbg_first; v.grp_cnt = c2.dbg_cnt;
     } else { v.cand = cx.cand; v.sort_idx = cx.sort_idx; v.sort_keys = cx.sort_keys; v.hitwords = cx.keys; v.grp_first = cx.grp_first; v.grp_cnt = cx.grp_cnt; }
