@@ -618,9 +618,43 @@ int smaltgpu_sw_pairframe_max_steps(int match, int mismatch, int gap_init, int g
 
 /* The candidate ranking sort of segAliCandsStats (segment.c:1733 -> sort.c:233): `narr` arrays of keys (< 1024), array t
  * in keys[off[t]..off[t+1]); returns the keys and the permutation (index into the array) in the reference's tie order
- * for ranks < nneed (all ranks if nneed < 0; ranks at or beyond nneed may be left unsorted).  in_lds: sort in LDS. */
+ * for ranks < nneed (all ranks if nneed < 0; ranks at or beyond nneed may be left unsorted).  in_lds: sort in LDS.
+ * instance 0: the sort as the candidate stage runs it.  instance 1: as the seeding stage runs it on the hit counts of a strand's
+ * seeds (hashhit.c:1040 -> sort.c:233) -- elements packed with 12 index bits, in LDS, all ranks (nneed and in_lds are not
+ * looked at): arrays of fewer than 4096 keys below 2^20, SMALTGPU_EARG otherwise. */
 int smaltgpu_rank_sort_batch(smaltgpu_mapper *m, const uint32_t *keys, const uint32_t *off, uint32_t narr, int nneed, int in_lds,
-                             uint32_t *out_keys, uint32_t *out_idx);
+                             int instance, uint32_t *out_keys, uint32_t *out_idx);
+
+/* S1 + S2 on their own (kernels k_encode and k_seed): the reads are uploaded and the two launches of a mapping call run on the
+ * mapper's own buffers, nothing behind them.  Before the launch the rows of the batch in the hit-info headers, the seed tables
+ * and the qualifier rows, and ONE row behind the last strand, are filled with the byte `guard`; all nrows = 2 * nreads + 1 rows
+ * come back, so what the kernel left alone still holds the guard.  The caller provides the arrays of smaltgpu_seed_out; their stride
+ * is out[6] of smaltgpu_cands_geometry.
+ * seed_range: [2 * nreads] (first, last) base as in smaltgpu_callctx, or NULL.  totals_only: the batch stops behind the
+ * lookups as in smaltgpu_hit_totals.  scratch_home 0: the stage's scratch where the mapper keeps it (LDS up to 48 KiB, HBM
+ * slots above); 1: HBM slots, allocated for this call where the mapper has none.  grid: workgroups, 0 = the launcher's choice.
+ * SMALTGPU_EARG: seed_range together with totals_only; a grid above the slot count when the scratch is in HBM; a read longer
+ * than the mapper's max_read_len; nreads >= the mapper's capacity (the guard row). */
+typedef struct smaltgpu_seed_out {
+  uint8_t *codes, *codes_rc;         /* [total bases] 3-bit codes, forward and reverse complement */
+  uint32_t *hi;                      /* [nrows][8]: n_seeds, seed_rank, status, qlen, nhit_rank, nhit_tot, nhit_cut, (unused) */
+  uint32_t *seeds;                   /* [nrows][stride][3]: posidx, nhits, qoffs in rank order */
+  uint8_t *qmask;                    /* [nrows][stride] */
+  uint32_t nrows, stride;
+  uint32_t in_lds, grid;             /* where the scratch was and how many workgroups ran */
+  uint64_t lookups;                  /* index lookups of the batch (work counter) */
+} smaltgpu_seed_out;
+int smaltgpu_seed_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
+                        const smaltgpu_params *par, const uint32_t *seed_range, int totals_only, int scratch_home, uint32_t grid,
+                        uint8_t guard, smaltgpu_seed_out *out);
+
+/* k_gather_reads on its own: two host batches (offsets from 0; qualities for both or neither) go up as the two resident batches
+ * of a block of pairs, the mapper's read buffers are filled with the byte `guard`, the kernel gathers reads `ids` (read
+ * ids[i] >> 1 of batch ids[i] & 1) and the result comes back: dst_off [nids + 1], dst_bases and dst_quals [dst_off[nids] + tail]
+ * (tail <= 16 bytes behind the last read, which must still hold the guard; without qualities dst_quals, if given, is all guard). */
+int smaltgpu_gather_batch(smaltgpu_mapper *m, const uint8_t *const bases[2], const uint8_t *const quals[2], const uint64_t *const read_off[2],
+                          const uint32_t nreads[2], const uint32_t *ids, uint32_t nids, uint8_t guard, uint32_t tail,
+                          uint8_t *dst_bases, uint8_t *dst_quals, uint64_t *dst_off);
 
 /* S3 on its own (kernel k_hits): the reads are uploaded and the launches of a mapping call run up to and including k_hits
  * (encode, seed, hits -- the mapper's own launchers, geometry and buffers, no other kernel); what the kernel left behind comes

@@ -463,3 +463,12 @@ void or_params_default(OrParams *p, const OrIndex *ix)
   p->flags = OR_FLG_BEST | ((ix->nseq < 512)? OR_FLG_SEQBYSEQ: 0); /* smalt.c:495-497, 599 */
   p->match = 1; p->mismatch = -2; p->gap_init = -4; p->gap_ext = -3; /* score.c:41-47 */
 }
+
+/* words in the bucket of `word`'s key (hashed index; tests that want absent words behind an occupied key) */
+uint32_t or_index_bucket_size(const OrIndex *ix, uint64_t word)
+{
+  uint32_t word_hi, key;
+  if (ix->typ == OR_IDX_PERFECT) return 0;
+  key = make_key(ix, word, &word_hi);
+  return ix->idx[key+1] - ix->idx[key];
+}

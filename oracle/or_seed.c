@@ -395,3 +395,66 @@ int or_collect_hits_cutoff(OrHitList *hl, OrHitInfo *hi, const OrIndex *ix, uint
   or_sort_u64(hl->nhits, hl->sqdat);
   return OR_OK;
 }
+
+/* Flat view of S1 + S2 of one read strand for tests that hold the seeding kernel against these routines (tests/seed_ref.py).
+ * noshort != 0: collectHitInfo alone with the stretch [seq_start, seq_end] (initRMAPINFO, rmap.c:1027-1044; 0, 0 = whole read),
+ * else hashCollectHitInfoShort.  hdr: n_seeds, seed_rank, status, qlen; seeds: [n_seeds][3] (posidx, nhits, qoffs) in the order
+ * of the seed index (rank order once sorted); qmask: [qlen + 1].  Returns OR_ERR_SHORTSEQ for a read shorter than a word. */
+int or_seed_flat(const OrIndex *ix, int is_reverse, int noshort, uint32_t ncut, uint32_t maxhit_total, int min_basq,
+                 uint32_t seq_start, uint32_t seq_end, const uint8_t *codes, const uint8_t *qual, uint32_t qlen,
+                 uint32_t *hdr, uint32_t *seeds, uint8_t *qmask)
+{
+  OrHitInfo hi;
+  uint32_t i;
+  int rv;
+  or_hitinfo_init(&hi, ix->s);
+  if (noshort) rv = or_collect_hitinfo(&hi, ix, is_reverse, ncut, min_basq, seq_start, seq_end, codes, qual, qlen);
+  else rv = or_collect_hitinfo_short(&hi, ix, is_reverse, ncut, maxhit_total, min_basq, codes, qual, qlen);
+  if (!rv) {
+    hdr[0] = hi.n_seeds; hdr[1] = hi.seed_rank; hdr[2] = (uint32_t) hi.status; hdr[3] = hi.qlen;
+    for (i = 0; i < hi.n_seeds; i++) {
+      const OrSeed *sp = hi.seed + hi.sidx[i];
+      seeds[3*i] = sp->posidx; seeds[3*i+1] = hi.sortkey[i]; seeds[3*i+2] = sp->qoffs;
+    }
+    memcpy(qmask, hi.qmask, (size_t) qlen + 1);
+  }
+  or_hitinfo_free(&hi);
+  return rv;
+}
+
+/* The recursion of the quicksort above as a wave walks it (smalt_amd/csrc/smg_wsort.hpp): ranges of more than 32 keys are
+ * partitioned as SORT_BODY does, ranges of 2..32 keys are listed and finished later.  Returns the number of listed ranges;
+ * `key` (n <= 4096) is left partly sorted.  The search for inputs with many such ranges (tests/golden/make_golden_seedsort.py)
+ * calls this a million times; tests/seed_ref.py restates it in Python. */
+int or_sort_listed_ranges(int n, uint32_t *key)
+{
+  int stk[256], sp = 0, lo = 0, hi = n - 1, i, j, mid, ranges = 0;
+  uint32_t pk, tk;
+#define SWP(a, b) tk = key[a]; key[a] = key[b]; key[b] = tk
+  for (;;) {
+    if (hi <= lo || hi - lo + 1 <= 32) {
+      if (hi > lo) ranges++;
+      if (!sp) return ranges;
+      hi = stk[--sp]; lo = stk[--sp];
+      continue;
+    }
+    mid = (lo + hi) >> 1;
+    SWP(mid, lo + 1);
+    if (key[lo] > key[hi]) { SWP(lo, hi); }
+    if (key[lo+1] > key[hi]) { SWP(lo + 1, hi); }
+    if (key[lo] > key[lo+1]) { SWP(lo, lo + 1); }
+    i = lo + 1; j = hi;
+    pk = key[lo+1];
+    for (;;) {
+      do i++; while (key[i] < pk);
+      do j--; while (key[j] > pk);
+      if (j < i) break;
+      SWP(i, j);
+    }
+    key[lo+1] = key[j]; key[j] = pk;
+    if (sp > 250) return -1;
+    if (hi - i + 1 >= j - lo) { stk[sp++] = i; stk[sp++] = hi; hi = j - 1; }
+    else { stk[sp++] = lo; stk[sp++] = j - 1; lo = i; }
+  }
+#undef SWP
+}

@@ -167,6 +167,14 @@ void or_ali_free(OrAli *a, int n);
 void or_score_matrix(int8_t M[8][8], int match, int mismatch);   /* score.c:138 */
 /* sorts with the reference's tie behaviour (sort.c:233, :415) */
 void or_sort2_u32(int n, uint32_t *key, uint32_t *val);
+/* ranges of 2..32 keys that the recursion of or_sort2_u32 reaches when longer ranges are partitioned first (or_seed.c) */
+int or_sort_listed_ranges(int n, uint32_t *key);
+/* S1 + S2 of one read strand as flat arrays (or_seed.c) */
+int or_seed_flat(const OrIndex *ix, int is_reverse, int noshort, uint32_t ncut, uint32_t maxhit_total, int min_basq,
+                 uint32_t seq_start, uint32_t seq_end, const uint8_t *codes, const uint8_t *qual, uint32_t qlen,
+                 uint32_t *hdr, uint32_t *seeds, uint8_t *qmask);
+/* words behind the key of `word` in a hashed index, 0 for a perfect one (or_index.c) */
+uint32_t or_index_bucket_size(const OrIndex *ix, uint64_t word);
 void or_sort_u64(int n, uint64_t *a);
 uint8_t or_code_of(unsigned char c);  /* sequence.c:287 */
 

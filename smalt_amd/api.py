@@ -138,6 +138,11 @@ class FineOut(C.Structure):            # smaltgpu_fine_out
                 ("fine_off", C.c_void_p), ("idx", C.c_void_p), ("pos", C.c_void_p)]
 
 
+class SeedOut(C.Structure):            # smaltgpu_seed_out
+    _fields_ = [("codes", C.c_void_p), ("codes_rc", C.c_void_p), ("hi", C.c_void_p), ("seeds", C.c_void_p), ("qmask", C.c_void_p),
+                ("nrows", C.c_uint32), ("stride", C.c_uint32), ("in_lds", C.c_uint32), ("grid", C.c_uint32), ("lookups", C.c_uint64)]
+
+
 HITRUN_NONE, HITRUN_SORTED, HITRUN_OVERFLOW = 0, 1, 2         # SMALTGPU_HITRUN_*
 SORT_REG4, SORT_REG8, SORT_REG16, SORT_LDS, SORT_HBM, SORT_CHUNKED = 0, 1, 2, 3, 4, 5        # forms of smaltgpu_sort_u64_batch
 
@@ -251,7 +256,11 @@ def lib():
         L.smaltgpu_band_geometry.argtypes = [C.c_int] * 10 + [C.POINTER(C.c_int32)]
         L.smaltgpu_sw_rowframe_max_steps.argtypes = [C.c_int] * 5
         L.smaltgpu_sw_pairframe_max_steps.argtypes = [C.c_int] * 5
-        L.smaltgpu_rank_sort_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.smaltgpu_rank_sort_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.smaltgpu_seed_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.c_void_p, C.c_int, C.c_int,
+                                          C.c_uint32, C.c_uint8, C.POINTER(SeedOut)]
+        L.smaltgpu_gather_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_void_p,
+                                            C.c_uint32, C.c_uint8, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.smaltgpu_hits_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.c_uint32, C.c_uint64,
                                           C.POINTER(HitsOut)]
         L.smaltgpu_fine_index_batch.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(Interval), C.c_uint32, C.c_uint32, C.POINTER(FineOut)]
@@ -713,15 +722,61 @@ class Mapper:
         return [dict(status=o.status, score=o.score, max_i=o.max_i, max_j=o.max_j, qs=o.qs, rs=o.rs,
                      diffstr=raw[o.stroffs:o.stroffs + o.dlen]) for o in out[:n]]
 
-    def rank_sort_batch(self, arrays, nneed: int = -1, in_lds: bool = True):
-        """Stand-alone candidate ranking sort: list of uint32 numpy arrays -> list of (keys, permutation)."""
+    def seed_batch(self, reads: Sequence[bytes], quals: Optional[Sequence[bytes]], params: Params, seed_range=None, totals_only: bool = False,
+                   scratch_home: int = 0, grid: int = 0, guard: int = 0xA5):
+        """Stand-alone S1 + S2 (smaltgpu_seed_batch): k_encode and k_seed over the reads, nothing else.  seed_range: (first, last)
+        per read.  scratch_home 1 forces the stage's scratch into HBM slots, grid is the number of workgroups (0: the launcher's
+        choice).  -> dict of numpy arrays: codes, codes_rc [bases]; off [n + 1]; hi [2n + 1][8] (n_seeds, seed_rank, status, qlen,
+        nhit_rank, nhit_tot, nhit_cut, unused), seeds [2n + 1][stride][3], qmask [2n + 1][stride] -- the last row is the guard row
+        behind the batch, everything was filled with the byte `guard` before the launch --; lookups, in_lds, grid, stride, guard."""
+        import numpy as np
+        n = len(reads)
+        bases, q, off = self._pack(reads, quals)
+        stride = self.cands_geometry()["qmax"]
+        rows, tot = 2 * n + 1, len(bases)
+        codes, codes_rc = np.zeros(tot + 1, np.uint8), np.zeros(tot + 1, np.uint8)
+        hi, seeds, qmask = np.zeros((rows, 8), np.uint32), np.zeros((rows, stride, 3), np.uint32), np.zeros((rows, stride), np.uint8)
+        sr = None
+        if seed_range is not None:
+            sr = np.ascontiguousarray(np.asarray(seed_range, dtype=np.uint32).reshape(n, 2))
+        out = SeedOut(codes.ctypes.data, codes_rc.ctypes.data, hi.ctypes.data, seeds.ctypes.data, qmask.ctypes.data)
+        _check(lib().smaltgpu_seed_batch(self.h, bases, q, off, n, C.byref(params), None if sr is None else sr.ctypes.data, int(totals_only), scratch_home,
+                                         grid, guard, C.byref(out)))
+        assert out.nrows == rows and out.stride == stride
+        return dict(codes=codes[:tot], codes_rc=codes_rc[:tot], off=np.array(list(off), dtype=np.int64), hi=hi, seeds=seeds, qmask=qmask,
+                    lookups=int(out.lookups), in_lds=bool(out.in_lds), grid=int(out.grid), stride=stride, guard=guard)
+
+    def gather_batch(self, batches, ids, guard: int = 0xA5, tail: int = 16):
+        """Stand-alone k_gather_reads (smaltgpu_gather_batch).  batches: two (bases uint8 array, quals uint8 array or None, offsets
+        uint64 array from 0); ids: read ids[i] >> 1 of batch ids[i] & 1.  -> (dst_bases, dst_quals, dst_off): the gathered bytes
+        with `tail` bytes behind the last read, which were filled with the byte `guard` before the launch (dst_quals: all guard
+        when the batches have no qualities)."""
+        import numpy as np
+        (b0, q0, o0), (b1, q1, o1) = batches
+        o = [np.ascontiguousarray(o0, dtype=np.uint64), np.ascontiguousarray(o1, dtype=np.uint64)]
+        b = [np.ascontiguousarray(np.concatenate([x, np.zeros(1, np.uint8)]), dtype=np.uint8) for x in (b0, b1)]
+        qs = None if q0 is None else [np.ascontiguousarray(np.concatenate([x, np.zeros(1, np.uint8)]), dtype=np.uint8) for x in (q0, q1)]
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        lens = [int(o[i & 1][(i >> 1) + 1] - o[i & 1][i >> 1]) for i in ids.tolist()]
+        tot = sum(lens)
+        db, dq, do = np.zeros(tot + tail, np.uint8), np.zeros(tot + tail, np.uint8), np.zeros(len(ids) + 1, np.uint64)
+        vp = lambda arrs: (C.c_void_p * 2)(*[a.ctypes.data for a in arrs])
+        nr = (C.c_uint32 * 2)(len(o[0]) - 1, len(o[1]) - 1)
+        idp = ids.ctypes.data if ids.size else np.zeros(1, np.uint32).ctypes.data
+        _check(lib().smaltgpu_gather_batch(self.h, vp(b), None if qs is None else vp(qs), vp(o), nr, idp, len(ids), guard, tail,
+                                           db.ctypes.data, dq.ctypes.data, do.ctypes.data))
+        return db, dq, do
+
+    def rank_sort_batch(self, arrays, nneed: int = -1, in_lds: bool = True, instance: int = 0):
+        """Stand-alone candidate ranking sort: list of uint32 numpy arrays -> list of (keys, permutation).  instance 1: the sort
+        as the seeding stage instantiates it (12 index bits, lists of 32 short ranges, in LDS; keys below 2^20, fewer than 4096)."""
         import numpy as np
         off = np.zeros(len(arrays) + 1, dtype=np.uint32)
         off[1:] = np.cumsum([len(a) for a in arrays])
         keys = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros(0), dtype=np.uint32)
         ok = np.zeros(max(1, keys.size), dtype=np.uint32)
         oi = np.zeros(max(1, keys.size), dtype=np.uint32)
-        _check(lib().smaltgpu_rank_sort_batch(self.h, keys.ctypes.data, off.ctypes.data, len(arrays), nneed, int(in_lds),
+        _check(lib().smaltgpu_rank_sort_batch(self.h, keys.ctypes.data, off.ctypes.data, len(arrays), nneed, int(in_lds), instance,
                                               ok.ctypes.data, oi.ctypes.data))
         return [(ok[off[t]:off[t + 1]], oi[off[t]:off[t + 1]]) for t in range(len(arrays))]
 

@@ -1461,19 +1461,22 @@ extern "C" int smaltgpu_sw_pairframe_max_steps(int match, int mismatch, int gap_
 }
 
 extern "C" int smaltgpu_rank_sort_batch(smaltgpu_mapper *m, const uint32_t *keys, const uint32_t *off, uint32_t narr, int nneed, int in_lds,
-                                         uint32_t *out_keys, uint32_t *out_idx) {
+                                         int instance, uint32_t *out_keys, uint32_t *out_idx) {
   if (!m || !keys || !off || !out_keys || !out_idx) return fail(SMALTGPU_EARG, "null argument");
+  if (instance != 0 && instance != 1) return fail(SMALTGPU_EARG, "unknown instance %d", instance);
   HIPCHK(hipSetDevice(m->device));
   const size_t tot = off[narr];
-  for (uint32_t t = 0; t < narr; t++) if (off[t + 1] < off[t] || off[t + 1] - off[t] > (1u << 22)) return fail(SMALTGPU_EARG, "bad array offsets");
-  for (size_t i = 0; i < tot; i++) if (keys[i] >= 1024u) return fail(SMALTGPU_EARG, "key out of range");
+  const uint32_t nlim = instance ? (1u << SEED_IDXBITS) - 1u : (1u << 22), klim = instance ? 1u << (32 - SEED_IDXBITS) : 1024u;
+  for (uint32_t t = 0; t < narr; t++) if (off[t + 1] < off[t] || off[t + 1] - off[t] > nlim) return fail(SMALTGPU_EARG, "bad array offsets");
+  for (size_t i = 0; i < tot; i++) if (keys[i] >= klim) return fail(SMALTGPU_EARG, "key out of range");
   uint32_t *dk = nullptr, *doff = nullptr, *dkv = nullptr, *dok = nullptr, *doi = nullptr;
   int rv = 0;
   if (dalloc(&dk, tot + 1) || dalloc(&doff, (size_t)narr + 1) || dalloc(&dkv, tot + 1) || dalloc(&dok, tot + 1) || dalloc(&doi, tot + 1)) rv = SMALTGPU_ENOMEM;
   if (!rv) {
     (void)hipMemcpy(dk, keys, tot * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(doff, off, ((size_t)narr + 1) * 4, hipMemcpyHostToDevice);
-    launch_rank_sort_raw(m->stream, dk, doff, narr, nneed, in_lds, dkv, dok, doi);
+    if (instance) launch_seed_sort_raw(m->stream, dk, doff, narr, dok, doi);
+    else launch_rank_sort_raw(m->stream, dk, doff, narr, nneed, in_lds, dkv, dok, doi);
     if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
     else { (void)hipMemcpy(out_keys, dok, tot * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(out_idx, doi, tot * 4, hipMemcpyDeviceToHost); }
   }
@@ -1608,5 +1611,114 @@ extern "C" int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys,
     else if (tot) (void)hipMemcpy(out, dout, tot * 8, hipMemcpyDeviceToHost);
   }
   (void)hipFree(dk); (void)hipFree(dout); (void)hipFree(doff);
+  return rv;
+}
+
+// S1 + S2 on their own: launch_encode and launch_seed on the mapper's buffers and nothing behind them.  The rows of the batch in
+// hi, seeds and qmask and one row behind the last strand are filled with `guard` first, so that a test sees every byte the kernel wrote.
+extern "C" int smaltgpu_seed_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
+                                   const smaltgpu_params *par, const uint32_t *seed_range, int totals_only, int scratch_home, uint32_t grid,
+                                   uint8_t guard, smaltgpu_seed_out *out) {
+  static_assert(sizeof(HitInfoHdr) == 8 * sizeof(uint32_t) && sizeof(SeedRec) == 3 * sizeof(uint32_t), "seed record layout");
+  if (!m || !bases || !read_off || !par || !out || !out->codes || !out->codes_rc || !out->hi || !out->seeds || !out->qmask) return fail(SMALTGPU_EARG, "null argument");
+  if (seed_range && totals_only) return fail(SMALTGPU_EARG, "seed_range and totals_only exclude each other (rmap.c:1076 counts the hits of whole reads)");
+  if (scratch_home != 0 && scratch_home != 1) return fail(SMALTGPU_EARG, "scratch_home is 0 or 1");
+  if (nreads >= m->max_reads || read_off[nreads] - read_off[0] > m->max_bases) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity (one guard row is kept behind the last strand)");
+  int rv = check_par(m, par);
+  if (rv) return rv;
+  const bool hbm = scratch_home == 1 || m->seed_bytes > 48 * 1024;
+  if (hbm && grid > m->seed_slots) return fail(SMALTGPU_EARG, "grid %u exceeds the %u scratch slots", grid, m->seed_slots);
+  const uint64_t total = read_off[nreads] - read_off[0];
+  m->h_off.resize((size_t)nreads + 1);
+  for (uint32_t i = 0; i <= nreads; i++) {
+    m->h_off[i] = read_off[i] - read_off[0];
+    if (i && m->h_off[i] - m->h_off[i - 1] > m->max_len) return fail(SMALTGPU_EARG, "read %u is longer than the mapper's max_read_len", i - 1);
+  }
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  if (total) HIPCHK(hipMemcpyAsync(m->d_bases, bases + read_off[0], total, hipMemcpyHostToDevice, s));
+  if (quals && total) HIPCHK(hipMemcpyAsync(m->d_quals, quals + read_off[0], total, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(m->d_off, m->h_off.data(), ((size_t)nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  if (seed_range) {
+    if (m->cx_seedrange.ensure((size_t)(nreads ? nreads : 1) * 8)) return fail(SMALTGPU_ENOMEM, "device memory");
+    if (nreads) HIPCHK(hipMemcpyAsync(m->cx_seedrange.p, seed_range, (size_t)nreads * 8, hipMemcpyHostToDevice, s));
+  }
+  Batch &b = m->b;
+  const DevIndex &d = m->ix->d;
+  const MapPar p = to_par(par);
+  b.iv_off = nullptr; b.iv = nullptr; b.min_sw = nullptr; b.prevmax = nullptr; b.fine_idx = nullptr; b.fine_pos = nullptr; b.fine_off = nullptr;
+  b.alloc_len = nullptr; b.seed_range = seed_range ? (const uint32_t *)m->cx_seedrange.p : nullptr; b.totals_only = totals_only ? 1u : 0u; b.raw_results = 0;
+  b.hitrun = nullptr;
+  m->last_fine = false; m->last_par = p; m->last_n = nreads; m->have_host_off = true; m->fetch_open = false;
+  b.nreads = nreads; b.codes = m->d_codes; b.codes_rc = m->d_codes_rc; b.qual = quals ? m->d_quals : nullptr; b.read_off = m->d_off;
+  const size_t rows = 2 * (size_t)nreads + 1, stride = m->qmax;
+  HIPCHK(hipMemsetAsync(m->d_counters, 0, smaltgpu_mapper::CT_BYTES, s));
+  HIPCHK(hipMemsetAsync(b.hi, guard, rows * sizeof(HitInfoHdr), s));
+  HIPCHK(hipMemsetAsync(b.seeds, guard, rows * stride * sizeof(SeedRec), s));
+  HIPCHK(hipMemsetAsync(b.qmask, guard, rows * stride, s));
+  // scratch: the mapper's own, or HBM slots for this call only where the mapper's fits LDS
+  uint8_t *scr = m->seed_scr, *own = nullptr;
+  const uint32_t items = 2 * nreads;
+  const uint32_t g = grid ? grid : (hbm ? (items < m->seed_slots ? items : m->seed_slots) : (items < 32768u ? items : 32768u));
+  if (scratch_home == 1 && !scr && g) {
+    HIPCHK(hipMalloc((void **)&own, m->seed_bytes * (size_t)g));
+    scr = own;
+  }
+  rv = launch_encode(s, m->d_bases, m->d_off, nreads, m->d_codes, m->d_codes_rc);
+  if (!rv) rv = launch_seed(s, b, d, p, scr, m->seed_bytes, own ? g : m->seed_slots, scratch_home == 1, grid);
+  b.seed_range = nullptr; b.totals_only = 0;
+  hipError_t he = hipStreamSynchronize(s);
+  if (own) (void)hipFree(own);
+  if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
+  HIPCHK(he);
+  unsigned long long work[WK_NWORK];
+  if (total) { HIPCHK(hipMemcpy(out->codes, m->d_codes, total, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out->codes_rc, m->d_codes_rc, total, hipMemcpyDeviceToHost)); }
+  HIPCHK(hipMemcpy(out->hi, b.hi, rows * sizeof(HitInfoHdr), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out->seeds, b.seeds, rows * stride * sizeof(SeedRec), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out->qmask, b.qmask, rows * stride, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(work, b.work, sizeof(work), hipMemcpyDeviceToHost));
+  out->nrows = (uint32_t)rows; out->stride = (uint32_t)stride; out->in_lds = hbm ? 0u : 1u; out->grid = nreads ? g : 0u; out->lookups = work[WK_LOOKUPS];
+  return SMALTGPU_OK;
+}
+
+// k_gather_reads on its own: the two host batches become the two resident batches, the mapper's read buffers are filled with
+// `guard`, launch_gather_reads runs with `ids`, and the gathered bytes come back with the `tail` bytes behind the last read
+extern "C" int smaltgpu_gather_batch(smaltgpu_mapper *m, const uint8_t *const bases[2], const uint8_t *const quals[2], const uint64_t *const read_off[2],
+                                     const uint32_t nreads[2], const uint32_t *ids, uint32_t nids, uint8_t guard, uint32_t tail,
+                                     uint8_t *dst_bases, uint8_t *dst_quals, uint64_t *dst_off) {
+  if (!m || !bases || !read_off || !nreads || !ids || !dst_bases || !dst_off || !bases[0] || !bases[1] || !read_off[0] || !read_off[1]) return fail(SMALTGPU_EARG, "null argument");
+  if (quals && (!quals[0] != !quals[1])) return fail(SMALTGPU_EARG, "qualities: both batches or neither");
+  const bool wq_in = quals && quals[0];
+  if (wq_in && !dst_quals) return fail(SMALTGPU_EARG, "null argument");
+  if (nids > m->max_reads || tail > 16) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity");
+  for (int w = 0; w < 2; w++) if (read_off[w][0] != 0) return fail(SMALTGPU_EARG, "offsets start at 0");
+  HIPCHK(hipSetDevice(m->device));
+  uint8_t *db[2] = {nullptr, nullptr}, *dq[2] = {nullptr, nullptr};
+  uint64_t *dof[2] = {nullptr, nullptr};
+  int rv = 0;
+  for (int w = 0; w < 2 && !rv; w++) {
+    const size_t tot = read_off[w][nreads[w]];
+    if (dalloc(&db[w], tot + 16) || dalloc(&dof[w], (size_t)nreads[w] + 1) || (wq_in && dalloc(&dq[w], tot + 16))) { rv = SMALTGPU_ENOMEM; break; }
+    if (tot) (void)hipMemcpy(db[w], bases[w], tot, hipMemcpyHostToDevice);
+    if (tot && wq_in) (void)hipMemcpy(dq[w], quals[w], tot, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dof[w], read_off[w], ((size_t)nreads[w] + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
+  }
+  if (!rv) {
+    smaltgpu_resident_reads src;
+    memset(&src, 0, sizeof(src));
+    for (int w = 0; w < 2; w++) { src.d_bases[w] = db[w]; src.d_quals[w] = dq[w]; src.d_read_off[w] = dof[w]; src.read_off[w] = read_off[w]; src.nreads[w] = nreads[w]; }
+    bool wq = false;
+    if (hipMemsetAsync(m->d_bases, guard, m->max_bases + 16, m->stream) != hipSuccess || hipMemsetAsync(m->d_quals, guard, m->max_bases + 16, m->stream) != hipSuccess)
+      rv = fail(SMALTGPU_ENODEV, "memset failed");
+    if (!rv) rv = gather_round(m, &src, ids, nids, &wq);
+    if (!rv && hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
+    if (!rv) {
+      const size_t tot = m->h_off[nids];
+      (void)hipMemcpy(dst_bases, m->d_bases, tot + tail, hipMemcpyDeviceToHost);
+      if (dst_quals) (void)hipMemcpy(dst_quals, m->d_quals, tot + tail, hipMemcpyDeviceToHost);      // (without qualities: the guard, untouched)
+      memcpy(dst_off, m->h_off.data(), ((size_t)nids + 1) * sizeof(uint64_t));
+    }
+  }
+  for (int w = 0; w < 2; w++) { (void)hipFree(db[w]); (void)hipFree(dq[w]); (void)hipFree(dof[w]); }
   return rv;
 }

@@ -15,7 +15,10 @@ int launch_gather_reads(hipStream_t s, uint8_t *dst_bases, uint8_t *dst_quals, c
 // needs b.iv_off/iv, b.fine_idx/fine_pos/fine_off; grid: workgroups (test hook), 0 = one per read up to 65535
 int launch_fine_index(hipStream_t s, const Batch &b, const DevIndex &ix, uint32_t grid = 0);
 inline uint32_t fine_index_grid(uint32_t nreads, uint32_t grid) { const uint32_t g = grid && grid < 65535u ? grid : 65535u; return nreads < g ? nreads : g; }
-int launch_seed(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, size_t sbytes, uint32_t nslots);
+// force_hbm: scratch in the HBM slots even where it would fit LDS; grid_fixed: that many workgroups, 0 = the launcher's own choice
+// (test hooks of smaltgpu_seed_batch; an HBM launch of more workgroups than slots is refused)
+int launch_seed(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, size_t sbytes, uint32_t nslots, int force_hbm = 0,
+                uint32_t grid_fixed = 0);
 struct CandGeom {              // scratch geometry of the candidate stage (both code paths share one HBM slot)
   uint32_t hcap;               // hits of both strands, power of two (sequential path)
   uint32_t hcap_strand;        // hits of one strand (wave-parallel path)
@@ -71,5 +74,8 @@ int launch_sort_u64_raw(hipStream_t s, const uint64_t *keys, const uint32_t *off
 // ... and of the sorts of the HBM working set, in place on global memory (in `out`), any length: form 4 = wave_sort_u64,
 // 5 = wave_sort_u64_chunked (smg_sortraw.hip: a translation unit of its own, see there)
 int launch_sort_u64_hbm_raw(hipStream_t s, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out);
+// test entry of the seed ranking's instance of the wave sort, wave_sort_kv<SEED_IDXBITS, SEED_LISTCAP, SEED_LSTK> in LDS as in
+// stage_seed: arrays of fewer than 4096 keys below 2^20 (smg_sortraw.hip)
+int launch_seed_sort_raw(hipStream_t s, const uint32_t *keys, const uint32_t *off, uint32_t narr, uint32_t *out_key, uint32_t *out_idx);
 
 }  // namespace smg

@@ -1806,11 +1806,17 @@ int launch_gather_reads(hipStream_t s, uint8_t *dst_bases, uint8_t *dst_quals, c
   return 0;
 }
 
-int launch_seed(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, size_t sbytes, uint32_t nslots) {
+int launch_seed(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, size_t sbytes, uint32_t nslots, int force_hbm,
+                uint32_t grid_fixed) {
   if (!b.nreads) return 0;
-  const int use_lds = sbytes <= 48 * 1024;
+  const int use_lds = sbytes <= 48 * 1024 && !force_hbm;
   uint32_t items = 2 * b.nreads;
   uint32_t grid = use_lds ? (items < 32768u ? items : 32768u) : (items < nslots ? items : nslots);
+  if (grid_fixed) {                                      // test entry (smaltgpu_seed_batch): a workgroup of an HBM launch owns slot blockIdx.x
+    if (!use_lds && (grid_fixed > nslots || !scratch)) return (int)hipErrorInvalidValue;
+    grid = grid_fixed;
+  }
+  if (!use_lds && !scratch) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_seed, dim3(grid), dim3(64), use_lds ? sbytes + LDS_GUARD : 0, s, b, ix, p, scratch, sbytes, use_lds);
   SMG_LAUNCH_CHECK();
   return 0;

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "smg_kernels.h"
 #include "smg_exec.h"
+#include "smg_stages.hpp"
 
 namespace smg {
 
@@ -32,6 +33,33 @@ int launch_sort_u64_hbm_raw(hipStream_t s, const uint64_t *keys, const uint32_t 
   if (!narr) return 0;
   if (form != 4 && form != 5) return -1;
   hipLaunchKernelGGL(k_sort_u64_hbm_raw, dim3(narr < 4096 ? narr : 4096), dim3(64), 0, s, keys, off, narr, form, out);
+  hipError_t e = hipGetLastError();
+  return e != hipSuccess ? (int)e : 0;
+}
+
+// The seed ranking's instance of the wave sort (stage_seed, wave form): elements packed (key << SEED_IDXBITS) | i in LDS, the
+// work words sized as the stage's (SEED_WSORT_WORDS).  With SEED_LISTCAP = 32 short ranges the list of short ranges is flushed in
+// the middle of the recursion; the default instance of the candidate ranking (k_rank_sort_raw) never gets there on such arrays.
+// The host has checked n < 2^SEED_IDXBITS and keys < 2^(32 - SEED_IDXBITS).
+__global__ void __launch_bounds__(64) k_seed_sort_raw(const uint32_t *keys, const uint32_t *off, uint32_t narr, uint32_t *out_key, uint32_t *out_idx) {
+  __shared__ uint32_t sh[16 + SEED_WSORT_WORDS + (1 << SEED_IDXBITS)];
+  uint32_t *wk = sh + 16, *a = wk + SEED_WSORT_WORDS;
+  for (uint32_t t = blockIdx.x; t < narr; t += gridDim.x) {
+    const uint32_t o = off[t];
+    uint32_t n = off[t + 1] - o;
+    if (n > (1u << SEED_IDXBITS) - 1u) n = (1u << SEED_IDXBITS) - 1u;
+    for (uint32_t i = threadIdx.x; i < n; i += 64) a[i] = (keys[o + i] << SEED_IDXBITS) | i;
+    __syncthreads();
+    wave_sort_kv<SEED_IDXBITS, SEED_LISTCAP, SEED_LSTK>(a, (int)n, (int)n, wk);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += 64) { out_key[o + i] = a[i] >> SEED_IDXBITS; out_idx[o + i] = a[i] & ((1u << SEED_IDXBITS) - 1u); }
+    __syncthreads();
+  }
+}
+
+int launch_seed_sort_raw(hipStream_t s, const uint32_t *keys, const uint32_t *off, uint32_t narr, uint32_t *out_key, uint32_t *out_idx) {
+  if (!narr) return 0;
+  hipLaunchKernelGGL(k_seed_sort_raw, dim3(narr < 4096 ? narr : 4096), dim3(64), 0, s, keys, off, narr, out_key, out_idx);
   hipError_t e = hipGetLastError();
   return e != hipSuccess ? (int)e : 0;
 }

@@ -79,6 +79,7 @@ int main(int argc, char **argv) {
     if (len > qmaxlen) qmaxlen = len;
   }
   fclose(fp);
+  free(l1); free(l2); free(l3); free(l4);
   const uint32_t n = (uint32_t)names.size();
   const uint32_t qmax = qmaxlen + 8;
   const bool seqbyseq = (p.flags & FLG_SEQBYSEQ) != 0;
@@ -112,6 +113,41 @@ int main(int argc, char **argv) {
   b.work = workctr; b.long_list = nullptr; b.long_cap = 0; b.strip_list = nullptr; b.strip_cap = 0; b.tile_qmax = 512;
 
   std::vector<uint8_t> sscr(seed_scratch_bytes(qmax, ix.s));
+  // EMU_SEED_DUMP=<file>: the seeding stage alone (tests/test_seed_paths.py).  Header rows, seed tables and qualifier rows are
+  // filled with the byte 0xA5 first, one row behind the last strand included; stage_seed runs over every strand with ONE scratch
+  // block, as a persistent workgroup does; then the arrays are written as they are and the program ends.  EMU_SEED_RANGE=<file>:
+  // line r holds `first last` of read r (Batch::seed_range); EMU_TOTALS=1: Batch::totals_only.
+  if (const char *sd = getenv("EMU_SEED_DUMP")) {
+    const size_t rows = 2 * (size_t)n + 1;
+    hi.resize(rows); seeds.resize(rows * qmax); qmask.resize(rows * qmax);
+    memset((void *)hi.data(), 0xA5, rows * sizeof(HitInfoHdr)); memset((void *)seeds.data(), 0xA5, rows * qmax * sizeof(SeedRec)); memset(qmask.data(), 0xA5, rows * qmax);
+    b.hi = hi.data(); b.seeds = seeds.data(); b.qmask = qmask.data();
+    std::vector<uint32_t> srange;
+    if (const char *rf = getenv("EMU_SEED_RANGE")) {
+      FILE *f = fopen(rf, "r");
+      if (!f) { fprintf(stderr, "emu: cannot read %s\n", rf); return 1; }
+      unsigned a, z;
+      while (fscanf(f, "%u %u", &a, &z) == 2) { srange.push_back(a); srange.push_back(z); }
+      fclose(f);
+      if (srange.size() != 2 * (size_t)n) { fprintf(stderr, "emu: %s holds %zu ranges for %u reads\n", rf, srange.size() / 2, n); return 1; }
+      if (srange.empty()) srange.resize(2);
+      b.seed_range = srange.data();
+    }
+    b.totals_only = getenv("EMU_TOTALS") && atoi(getenv("EMU_TOTALS")) != 0;
+    if (b.seed_range && b.totals_only) { fprintf(stderr, "emu: EMU_SEED_RANGE and EMU_TOTALS exclude each other\n"); return 1; }
+    SeedScratch sx = seed_scratch_carve(sscr.data(), qmax, ix.s);
+    unsigned long long nlook = 0;
+    for (uint32_t rs = 0; rs < 2 * n; rs++) nlook += stage_seed(b, ix, p, rs >> 1, rs & 1, sx);
+    // "SMGSEED1", u32 rows, stride, u64 bases, lookups; u8 codes[bases], codes_rc[bases]; HitInfoHdr hi[rows]; SeedRec seeds[rows][stride]; u8 qmask[rows][stride]
+    FILE *hf = fopen(sd, "wb");
+    if (!hf) { fprintf(stderr, "emu: cannot write %s\n", sd); return 1; }
+    const uint32_t head[2] = {(uint32_t)rows, qmax};
+    const uint64_t cnt[2] = {off.back(), nlook};
+    fwrite("SMGSEED1", 1, 8, hf); fwrite(head, 4, 2, hf); fwrite(cnt, 8, 2, hf);
+    fwrite(codes.data(), 1, codes.size(), hf); fwrite(codes_rc.data(), 1, codes_rc.size(), hf);
+    fwrite(hi.data(), sizeof(HitInfoHdr), rows, hf); fwrite(seeds.data(), sizeof(SeedRec), rows * qmax, hf); fwrite(qmask.data(), 1, rows * qmax, hf);
+    return fclose(hf) ? 1 : 0;
+  }
   // EMU_INTERVALS=<file>: every read is one of rmapPair's restricted calls over the main index (rmap.c:438-492); line r of the
   // file holds the search intervals of read r as `sx lo hi` triples (0-based, inclusive; an empty line: no interval, no seeds).
   // EMU_CANDCAP / EMU_LDS_BYTES: candidates per slot and bytes of the block that stands for LDS (restricted calls keep the

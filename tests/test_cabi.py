@@ -14,6 +14,7 @@ def test_library_exports_declared_symbols():
     declared = sorted(set(re.findall(r"\b(smaltgpu_[a-z0-9_]+)\s*\(", hdr)))
     assert len(declared) >= 15
     assert "smaltgpu_hits_batch" in declared and "smaltgpu_sort_u64_batch" in declared
+    assert "smaltgpu_seed_batch" in declared and "smaltgpu_gather_batch" in declared and "smaltgpu_rank_sort_batch" in declared
     lib = ctypes.CDLL(os.path.join(ROOT, "smalt_amd", "libsmaltgpu.so"))
     for name in declared:
         assert hasattr(lib, name), name
