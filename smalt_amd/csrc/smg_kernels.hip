@@ -260,11 +260,89 @@ __global__ void __launch_bounds__(64) k_align(Batch b, DevIndex ix, MapPar p, ui
 // beyond the read are fed 'N' (score 0), which can never raise the maximum, so lanes need no
 // predication.  int32 arithmetic equals the reference's 8-bit pass, and its 16-bit re-run on
 // saturation, for any score < 65535.
+//
+// The stand-alone entries of the parity tests (smaltgpu_sw_*_raw -> k_sw_full_raw, k_sw_full16_raw) run the sweep
+// bodies of the production kernels (SW32_CORE; sw16_tabs, sw16_nstep, sw16_sweep): a kernel and its entry differ only
+// in where a task comes from, how its window and selectors get into LDS and registers, and where its score goes.
 // ---------------------------------------------------------------------------------------
-template <int G>
-__device__ inline int shr1(int v) {          // value of the lane to the left inside a 16-lane row
-  return __builtin_amdgcn_update_dpp(0, v, 0x111 /* row_shr:1 */, 0xf, 0xf, true);
+// the score matrix is kept biased so that every entry fits an unsigned byte: bias >= -min(M)
+__host__ __device__ inline int sw_bias(const MapPar &p) {
+  return p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match);
 }
+// a task's window starts here in the concatenated reference, and this is its read on the task's strand
+__device__ inline uint64_t sw_task_gbase(const DevIndex &ix, const RCand &c) { return (c.sqidx < 0 ? 0ull : ix.sop[c.sqidx]) + c.rs; }
+__device__ inline const uint8_t *sw_task_query(const Batch &b, const RCand &c) {
+  return ((c.flags & RCF_REVERSE) ? b.codes_rc : b.codes) + b.read_off[c.rid];
+}
+// window code of a byte of the stand-alone entries, as ref_code decodes the packed reference: 7 -> A, 4 and 6 -> N
+__device__ inline uint32_t sw_code_of_byte(uint32_t v) {
+  const uint32_t cd = v & 7u;
+  return cd == 7 ? 0 : (cd == 6 || cd == 4) ? 5 : cd;
+}
+// write-back of a scored K2a task (rc: its record, flags: as read from it) and its share of the two work counters
+__device__ inline void sw_store_score(RCand *rc, uint32_t flags, int best, uint32_t qlen, uint32_t wlen, unsigned long long &cells,
+                                      unsigned long long &ntasks_done) {
+  rc->swscor = best;
+  rc->flags = flags | RCF_SCORED | (best >= 65535 ? RCF_BANDED : 0u);   // ERRCODE_SWATEXCEED -> K2b
+  cells += (unsigned long long)qlen * wlen;
+  ntasks_done += best < 65535 ? 1 : 0;      /* a score that left 16 bits waits for K2b */
+}
+
+__device__ inline void sw_tab8(uint2 *tab, const MapPar &p, int bias) {
+  if (threadIdx.x < 8) {                     // biased score matrix rows (score.c:138-173; rows 4,6 = N, 7 = A)
+    const int lane = (int)threadIdx.x;
+    const int rb = lane == 7 ? 0 : ((lane == 6 || lane == 4) ? 5 : lane);
+    uint32_t w[2] = {0, 0};
+    for (int qc = 0; qc < 8; qc++) {
+      const int v = (rb == 5 || qc >= 4) ? 0 : ((rb == qc) ? p.match : p.mismatch);
+      w[qc >> 2] |= (uint32_t)((v + bias) & 0xff) << (8 * (qc & 3));
+    }
+    tab[lane] = make_uint2(w[0], w[1]);
+  }
+}
+
+// value of the lane to the left inside a 16-lane row
+__device__ inline uint32_t shr1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, true); }
+
+// The sweep of one task by its G lanes, declaring `best` = the task's score in all lanes of the group: wrow = the window's
+// codes in LDS (wlen of them, written by these lanes just before), sel = the lane's C selectors, tab = the table of sw_tab8;
+// G and C are the tiling of the kernel around it.  Every lane of the workgroup runs it (the barrier, the wave-wide number
+// of steps).  A macro and not a function on purpose: a function, also a force-inlined one, is simplified on its own before
+// it is inlined, and the loop of k_sw_full<8,20> and <16,32> then comes out one instruction longer than from this text in
+// the kernel (the running maximum's chain of v_max3 ends in a two-operand v_max; profiles/k2a_shared_body_static.txt).
+#define SW32_CORE(best, wrow, wlen, sel, g, tab, bias, gi, ge)                                           \
+  int best = 0;                                                                                          \
+  {                                                                                                      \
+    int H[C], E[C];                                                                                      \
+    _Pragma("unroll") for (int cc = 0; cc < C; cc++) { H[cc] = 0; E[cc] = 0; }                           \
+    int F = 0, prev_hl = 0;                                                                              \
+    int nstep = (int)(wlen) + G - 1;                        /* wave-uniform number of steps */           \
+    for (int o = 32; o > 0; o >>= 1) nstep = max(nstep, __shfl_xor(nstep, o));                           \
+    __syncthreads();                                                                                     \
+    for (int step = 0; step < nstep; step++) {                                                           \
+      const int row = step - (g);                                                                        \
+      const uint32_t rb = (row >= 0 && row < (int)(wlen)) ? (wrow)[row] : 5u;                            \
+      const uint2 tr = (tab)[rb];                                                                        \
+      int hl = (int)shr1_u32((uint32_t)H[C - 1]);                                                        \
+      int fin = (int)shr1_u32((uint32_t)F);                                                              \
+      if ((g) == 0) { hl = 0; fin = 0; }                                                                 \
+      int diag = prev_hl;                                                                                \
+      prev_hl = hl;                                                                                      \
+      F = fin;                                                                                           \
+      _Pragma("unroll") for (int cc = 0; cc < C; cc++) {                                                 \
+        const int w = (int)__builtin_amdgcn_perm(tr.y, tr.x, (sel)[cc]);                                 \
+        const int h = diag + w - (bias);                                                                 \
+        const int hh = max(max(h, E[cc]), F);               /* v_max3_i32; E, F >= 0 keep H >= 0 */      \
+        best = max(best, hh);                                                                            \
+        diag = H[cc];                                                                                    \
+        H[cc] = hh;                                                                                      \
+        const int tt = hh - (gi);                                                                        \
+        E[cc] = max(max(E[cc] - (ge), tt), 0);                                                           \
+        F = max(max(F - (ge), tt), 0);                                                                   \
+      }                                                                                                  \
+    }                                                                                                    \
+    for (int o = G / 2; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));                           \
+  }
 
 template <int G, int C>
 __global__ void __launch_bounds__(64) k_sw_full(Batch b, DevIndex ix, MapPar p, uint32_t ntask_cap, int after16) {
@@ -276,17 +354,9 @@ __global__ void __launch_bounds__(64) k_sw_full(Batch b, DevIndex ix, MapPar p, 
   __shared__ uint2 tab[8];
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t ntask = min(*b.rc_count, ntask_cap);
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));   // >= -min(M)
+  const int bias = sw_bias(p);
   const int gi = -p.gap_init, ge = -p.gap_ext;
-  if (lane < 8) {                            // biased score matrix rows (score.c:138-173; rows 4,6 = N, 7 = A)
-    int rb = lane == 7 ? 0 : ((lane == 6 || lane == 4) ? 5 : lane);
-    uint32_t w[2] = {0, 0};
-    for (int qc = 0; qc < 8; qc++) {
-      int v = (rb == 5 || qc >= 4) ? 0 : ((rb == qc) ? p.match : p.mismatch);
-      w[qc >> 2] |= (uint32_t)((v + bias) & 0xff) << (8 * (qc & 3));
-    }
-    tab[lane] = make_uint2(w[0], w[1]);
-  }
+  sw_tab8(tab, p, bias);
   __syncthreads();
   const uint32_t ngroups = gridDim.x * NG;
   unsigned long long cells = 0, ntasks_done = 0;
@@ -301,7 +371,7 @@ __global__ void __launch_bounds__(64) k_sw_full(Batch b, DevIndex ix, MapPar p, 
       qlen = read_len(b, c.rid);
       wlen = (uint32_t)(c.re - c.rs + 1);
       live = !(c.flags & (RCF_BANDED | RCF_ERR | RCF_SCORED)) && wlen <= (uint32_t)WMAX && qlen <= (uint32_t)(G * C);
-      gbase = (c.sqidx < 0 ? 0ull : ix.sop[c.sqidx]) + c.rs;
+      gbase = sw_task_gbase(ix, c);
     }
     if (!live) { qlen = 0; wlen = 0; }
     // window -> LDS (sequence.c:1499 decode folded into the fetch)
@@ -309,56 +379,59 @@ __global__ void __launch_bounds__(64) k_sw_full(Batch b, DevIndex ix, MapPar p, 
     // query columns of this lane: selector byte = code (0..3 standard, 5 = N -> score 0 column)
     uint32_t sel[C];
     {
-      const uint8_t *q = ((c.flags & RCF_REVERSE) ? b.codes_rc : b.codes) + (live ? b.read_off[c.rid] : 0);
+      const uint8_t *q = live ? sw_task_query(b, c) : b.codes;      // a group without a task has no record to decode
 #pragma unroll
       for (int cc = 0; cc < C; cc++) {
         uint32_t j = (uint32_t)(g * C + cc);
-        uint32_t qc = (live && j < qlen) ? q[j] : 5u;
+        uint32_t qc = j < qlen ? q[j] : 5u;
         sel[cc] = 0x0c0c0c00u | qc;
       }
     }
-    int H[C], E[C];
-#pragma unroll
-    for (int cc = 0; cc < C; cc++) { H[cc] = 0; E[cc] = 0; }
-    int best = 0, F = 0, prev_hl = 0;
-    // wave-uniform number of steps
-    int nstep = (int)wlen + G - 1;
-    for (int o = 32; o > 0; o >>= 1) nstep = max(nstep, __shfl_xor(nstep, o));
-    __syncthreads();
-    for (int step = 0; step < nstep; step++) {
-      const int row = step - g;
-      const uint32_t rb = (row >= 0 && row < (int)wlen) ? win[grp][row] : 5u;
-      const uint2 tr = tab[rb];
-      int hl = shr1<G>(H[C - 1]);
-      int fin = shr1<G>(F);
-      if (g == 0) { hl = 0; fin = 0; }
-      int diag = prev_hl;
-      prev_hl = hl;
-      F = fin;
-#pragma unroll
-      for (int cc = 0; cc < C; cc++) {
-        const int w = (int)__builtin_amdgcn_perm(tr.y, tr.x, sel[cc]);
-        const int h = diag + w - bias;
-        const int hh = max(max(h, E[cc]), F);       // v_max3_i32; E, F >= 0 keep H >= 0
-        best = max(best, hh);
-        diag = H[cc];
-        H[cc] = hh;
-        const int tt = hh - gi;
-        E[cc] = max(max(E[cc] - ge, tt), 0);
-        F = max(max(F - ge, tt), 0);
-      }
-    }
-    for (int o = G / 2; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
-    if (live && g == 0) {
-      b.rcpool[t].swscor = best;
-      b.rcpool[t].flags = c.flags | RCF_SCORED | (best >= 65535 ? RCF_BANDED : 0u);   // ERRCODE_SWATEXCEED -> K2b
-      cells += (unsigned long long)qlen * wlen;
-      ntasks_done += best < 65535 ? 1 : 0;      /* a score that left 16 bits waits for K2b */
-    }
+    SW32_CORE(best, win[grp], wlen, sel, g, tab, bias, gi, ge)
+    if (live && g == 0) sw_store_score(b.rcpool + t, c.flags, best, qlen, wlen, cells, ntasks_done);
     __syncthreads();
   }
   for (int o = 32; o > 0; o >>= 1) { cells += __shfl_xor(cells, o); ntasks_done += __shfl_xor(ntasks_done, o); }
   if (lane == 0 && cells) { atomicAdd(b.work + WK_CELLS_FULL, cells); atomicAdd(b.work + WK_TASKS_FULL, ntasks_done); }
+}
+
+// stand-alone K2a over explicit (query, window) code arrays -- parity tests of the kernel
+template <int G, int C>
+__global__ void __launch_bounds__(64) k_sw_full_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
+                                                     const uint32_t *r_off, uint32_t ntask, MapPar p, int32_t *scores) {
+  constexpr int NG = 64 / G;
+  constexpr int WMAX = SW_FULL_WMAX;
+  __shared__ uint8_t win[NG][WMAX + 8];
+  __shared__ uint2 tab[8];
+  const int lane = threadIdx.x, g = lane % G, grp = lane / G;
+  const int bias = sw_bias(p);
+  const int gi = -p.gap_init, ge = -p.gap_ext;
+  sw_tab8(tab, p, bias);
+  __syncthreads();
+  const uint32_t ngroups = gridDim.x * NG;
+  for (uint32_t t0 = blockIdx.x * NG; t0 < ntask; t0 += ngroups) {
+    const uint32_t t = t0 + grp;
+    uint32_t qlen = 0, wlen = 0;
+    const uint8_t *q = qcodes, *r = rcodes;
+    bool live = false;
+    if (t < ntask) {
+      qlen = q_off[t + 1] - q_off[t]; wlen = r_off[t + 1] - r_off[t];
+      q += q_off[t]; r += r_off[t];
+      live = wlen <= (uint32_t)WMAX && qlen <= (uint32_t)(G * C);
+    }
+    if (!live) { qlen = 0; wlen = 0; }
+    for (uint32_t i = g; i < wlen; i += G) win[grp][i] = (uint8_t)sw_code_of_byte(r[i]);
+    uint32_t sel[C];
+#pragma unroll
+    for (int cc = 0; cc < C; cc++) {
+      uint32_t j = (uint32_t)(g * C + cc);
+      uint32_t qc = (j < qlen) ? (q[j] & 7u) : 5u;
+      sel[cc] = 0x0c0c0c00u | qc;
+    }
+    SW32_CORE(best, win[grp], wlen, sel, g, tab, bias, gi, ge)
+    if (t < ntask && g == 0) scores[t] = live ? best : -1;
+    __syncthreads();
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -391,7 +464,6 @@ __device__ inline us2 pk_max3(us2 a, us2 b, us2 c) {
   const hf2 r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(hf2, a), __builtin_bit_cast(hf2, b)), __builtin_bit_cast(hf2, c));
   return __builtin_bit_cast(us2, r);
 }
-__device__ inline uint32_t shr1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, true); }
 // The two lane hand-overs of a sweep row, each with its select in the same instruction: h = first lane of its group ?
 // hfirst : hv of the lane to the left, f likewise from its own value one lane to the left.  v_cndmask_b32 is VOP2 and
 // takes a DPP source here: dst = VCC ? src1 : dpp(src0).  The compiler does not form it from update_dpp and a select (it
@@ -487,7 +559,7 @@ __device__ inline Sw16Par sw16_par(const MapPar &p, int ncols = 512) {
   s.hi_pmatch = f16_bits_of_int(p.match - 2 * p.gap_ext) >> 8; s.hi_pmismatch = f16_bits_of_int(p.mismatch - 2 * p.gap_ext) >> 8;
   s.hi_pn = f16_bits_of_int(-2 * p.gap_ext) >> 8;
   { const uint32_t e = f16_bits_of_int(2 * p.gap_ext); s.nge2 = us2{(unsigned short)e, (unsigned short)e}; }      // - 2 ge
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
+  const int bias = sw_bias(p);
   s.mm4 = (uint32_t)((p.mismatch + bias) & 0xff) * 0x01010101u;      // a row of mismatches ...
   s.dlt = (uint32_t)(p.match - p.mismatch);                          // ... plus this at the byte of the matching base
   s.n4 = (uint32_t)(bias & 0xff) * 0x01010101u;                      // reference 'N': score 0 against everything
@@ -955,6 +1027,31 @@ __device__ inline void sw16_window(uint16_t *wrow, int g, uint32_t nent, const u
   }
 }
 
+// The score tables of the forms a launch may run (frames bit 0: row frame, bit 1: pair frame) and the longest sweep of
+// either frame, -1 where the form is off or does not hold these penalties.
+__device__ inline void sw16_tabs(uint2 *rowtab2, uint2 *rowtab2r, uint2 *rowtab2p, const Sw16Par &sp, int frames, int &rf_steps, int &pf_steps) {
+  sw16_rowtab2(rowtab2, sp);
+  rf_steps = (frames & 1) ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
+  pf_steps = (frames & 2) ? sp.pf_steps : -1;      // and up to this many in the pair frame, which goes first
+  if (rf_steps >= 0) sw16_rowtab2r(rowtab2r, sp);
+  if (pf_steps >= 0) sw16_rowtab2p(rowtab2p, sp);
+}
+// steps of the wave's sweep: the longest window among its tasks (wmax: the longer one of this group), the groups' skew
+template <int G>
+__device__ inline int sw16_nstep(uint32_t wmax) {
+  int nstep = (int)wmax + G - 1;
+  for (int o = 32; o > 0; o >>= 1) nstep = max(nstep, __shfl_xor(nstep, o));
+  return __builtin_amdgcn_readfirstlane(nstep);                          // wave-uniform: a scalar loop bound for the sweep
+}
+// The choice of form, by the sweep's length; nstep is wave-uniform (sw16_nstep): scalar branches.
+template <int G, int C>
+__device__ inline uint32_t sw16_sweep(const uint16_t *wrow, int nstep, const uint32_t (&sel)[C], int g, const Sw16Par &sp, int rf_steps, int pf_steps,
+                                      const uint2 *rowtab2, const uint2 *rowtab2r, const uint2 *rowtab2p) {
+  return nstep <= pf_steps ? sw16p_core<G, C>(wrow, nstep, sel, g, sp, rowtab2, rowtab2r, rowtab2p)
+         : nstep <= rf_steps ? sw16r_core<G, C>(wrow, nstep, sel, g, sp, rowtab2r)
+         : sp.fp ? sw16f_core<G, C>(wrow, nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(wrow, nstep, sel, g, sp, rowtab2);
+}
+
 template <int G, int C, int WMAX>
 __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p, uint32_t ntask_cap, int frames) {
   // the small-LDS instance (WMAX = SW_SHORT_WMAX) runs first; the large one only sees what is left
@@ -970,11 +1067,8 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t ntask = list ? (uint32_t)nlong : min(*b.rc_count, ntask_cap), npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
-  sw16_rowtab2(rowtab2, sp);
-  const int rf_steps = (frames & 1) ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
-  const int pf_steps = (frames & 2) ? sp.pf_steps : -1;      // and up to this many in the pair frame, which goes first
-  if (rf_steps >= 0) sw16_rowtab2r(rowtab2r, sp);
-  if (pf_steps >= 0) sw16_rowtab2p(rowtab2p, sp);
+  int rf_steps, pf_steps;
+  sw16_tabs(rowtab2, rowtab2r, rowtab2p, sp, frames, rf_steps, pf_steps);
   const uint32_t niter = (npair + NG - 1) / NG;                             // iterations of NG task pairs, dealt to the waves in turn
   const bool small = ix.totlen <= 0xffffffffull;
   const int64_t lastw = (int64_t)(ix.totlen / 10);
@@ -994,9 +1088,8 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
         const uint64_t rs = rc->rs;
         const uint32_t ql = read_len(b, r), wl = (uint32_t)(rc->re - rs + 1);
         if (!(flags & (RCF_BANDED | RCF_ERR | RCF_QN | RCF_SCORED)) && wl <= (uint32_t)WMAX && ql <= (uint32_t)(G * C)) {
-          const int32_t sq = rc->sqidx;
           int64_t wb; uint32_t s;
-          sw16_win_origin<G>((sq < 0 ? 0ull : ix.sop[sq]) + rs, small, wb, s);
+          sw16_win_origin<G>(sw_task_gbase(ix, *rc), small, wb, s);
           rid = r; wlo = (uint32_t)(uint64_t)wb; whi = (uint32_t)((uint64_t)wb >> 32);
           meta = ql | (wl << 10) | (s << 20) | ((flags & RCF_REVERSE) ? 1u << 24 : 0u) | (1u << 25);
         }
@@ -1013,10 +1106,7 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
       wbase[u] = (int64_t)(((uint64_t)(uint32_t)__shfl((int)whi, src) << 32) | (uint32_t)__shfl((int)wlo, src));
       qlen[u] = mt & 0x3ffu; wlen[u] = (mt >> 10) & 0x3ffu; ws[u] = (mt >> 20) & 0xfu; rev[u] = (mt >> 24) & 1u; live[u] = (mt >> 25) & 1u;
     }
-    const uint32_t wmax = wlen[0] > wlen[1] ? wlen[0] : wlen[1];
-    int nstep = (int)wmax + G - 1;
-    for (int o = 32; o > 0; o >>= 1) nstep = max(nstep, __shfl_xor(nstep, o));
-    nstep = __builtin_amdgcn_readfirstlane(nstep);                         // wave-uniform: a scalar loop bound for the sweep
+    const int nstep = sw16_nstep<G>(wlen[0] > wlen[1] ? wlen[0] : wlen[1]);
     sw16_window<G>(win[grp], g, (uint32_t)(nstep + G - 1), ix.packed, lastw, wbase, ws, wlen);
     // selectors: one pass per distinct read among the wave's tasks (nearly always one, and often the read staged already)
     uint32_t xa[NW], xb[NW];
@@ -1040,11 +1130,9 @@ __global__ void __launch_bounds__(64) k_sw_full16(Batch b, DevIndex ix, MapPar p
     uint32_t sel[C];
     sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
-    const uint32_t bb = nstep <= pf_steps ? sw16p_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2, rowtab2r, rowtab2p)      // nstep is wave-uniform: scalar branches
-                        : nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)
-                        : sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
+    const uint32_t bb = sw16_sweep<G, C>(win[grp], nstep, sel, g, sp, rf_steps, pf_steps, rowtab2, rowtab2r, rowtab2p);
     if ((meta >> 25) & 1u) {                                               // lanes 0 and 1 with a task of their own that was scored
-      const int best = (int)((bb >> (16 * g)) & 0xffffu);
+      const int best = (int)((bb >> (16 * g)) & 0xffffu);                   // as sw_store_score
       b.rcpool[tix].swscor = best;
       b.rcpool[tix].flags = flags | RCF_SCORED | (best >= 65535 ? RCF_BANDED : 0u);   // ERRCODE_SWATEXCEED -> K2b
       cells += (unsigned long long)(meta & 0x3ffu) * ((meta >> 10) & 0x3ffu);
@@ -1070,11 +1158,8 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
   const int lane = threadIdx.x, g = lane % G, grp = lane / G;
   const uint32_t npair = (ntask + 1) / 2;
   const Sw16Par sp = sw16_par(p, G * C);
-  sw16_rowtab2(rowtab2, sp);
-  const int rf_steps = (frames & 1) ? sp.rf_steps : -1;      // sweeps up to this many steps run in the row frame
-  const int pf_steps = (frames & 2) ? sp.pf_steps : -1;      // and up to this many in the pair frame, which goes first
-  if (rf_steps >= 0) sw16_rowtab2r(rowtab2r, sp);
-  if (pf_steps >= 0) sw16_rowtab2p(rowtab2p, sp);
+  int rf_steps, pf_steps;
+  sw16_tabs(rowtab2, rowtab2r, rowtab2p, sp, frames, rf_steps, pf_steps);
   const uint32_t ngroups = gridDim.x * NG;
   for (uint32_t t0 = blockIdx.x * NG; t0 < npair; t0 += ngroups) {
     const uint32_t tp = t0 + grp;
@@ -1091,15 +1176,12 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
       }
       if (!live[u]) { qlen[u] = 0; wlen[u] = 0; }
     }
-    const uint32_t wmax = wlen[0] > wlen[1] ? wlen[0] : wlen[1];
-    int nstep = (int)wmax + G - 1;
-    for (int o = 32; o > 0; o >>= 1) nstep = max(nstep, __shfl_xor(nstep, o));
-    nstep = __builtin_amdgcn_readfirstlane(nstep);                         // wave-uniform: a scalar loop bound for the sweep
+    const int nstep = sw16_nstep<G>(wlen[0] > wlen[1] ? wlen[0] : wlen[1]);
     for (uint32_t e = g; e < (uint32_t)(nstep + G - 1); e += G) {
       const uint32_t i = e - (uint32_t)(G - 1);
       uint32_t cd[2];
 #pragma unroll
-      for (int u = 0; u < 2; u++) { const uint32_t x = i < wlen[u] ? (r[u][i] & 7u) : 5u; cd[u] = x == 7 ? 0 : ((x == 6 || x == 4) ? 5 : x); }
+      for (int u = 0; u < 2; u++) cd[u] = i < wlen[u] ? sw_code_of_byte(r[u][i]) : 5u;
       win[grp][e] = (uint16_t)((cd[0] | (cd[1] << 3)) << 3);                // pair x 8, as sw16_window writes it
     }
     uint32_t xa[NW], xb[NW];
@@ -1121,9 +1203,7 @@ __global__ void __launch_bounds__(64) k_sw_full16_raw(const uint8_t *qcodes, con
     uint32_t sel[C];
     sw16_sel<G, C>(sel, xa, xb, sp.fp);
     __syncthreads();
-    const uint32_t bb = nstep <= pf_steps ? sw16p_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2, rowtab2r, rowtab2p)      // nstep is wave-uniform: scalar branches
-                        : nstep <= rf_steps ? sw16r_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2r)
-                        : sp.fp ? sw16f_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2) : sw16_core<G, C>(win[grp], nstep, sel, g, sp, rowtab2);
+    const uint32_t bb = sw16_sweep<G, C>(win[grp], nstep, sel, g, sp, rf_steps, pf_steps, rowtab2, rowtab2r, rowtab2p);
     if (g == 0) {
 #pragma unroll
       for (int u = 0; u < 2; u++) {
@@ -1217,19 +1297,6 @@ __device__ inline int sw_strip_core(const uint8_t *q, uint32_t qlen, const uint8
   }
   for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
   return best;
-}
-
-__device__ inline void sw_tab8(uint2 *tab, const MapPar &p, int bias) {
-  if (threadIdx.x < 8) {                     // biased score matrix rows (score.c:138-173; rows 4,6 = N, 7 = A)
-    const int lane = (int)threadIdx.x;
-    const int rb = lane == 7 ? 0 : ((lane == 6 || lane == 4) ? 5 : lane);
-    uint32_t w[2] = {0, 0};
-    for (int qc = 0; qc < 8; qc++) {
-      const int v = (rb == 5 || qc >= 4) ? 0 : ((rb == qc) ? p.match : p.mismatch);
-      w[qc >> 2] |= (uint32_t)((v + bias) & 0xff) << (8 * (qc & 3));
-    }
-    tab[lane] = make_uint2(w[0], w[1]);
-  }
 }
 
 // The same in packed 16-bit halves: two tasks per wave (as k_sw_full16; reads without non-ACGT codes, scores < 65535).
@@ -1352,8 +1419,8 @@ __global__ void __launch_bounds__(64) k_sw_strip16(Batch b, DevIndex ix, MapPar 
         qlen[u] = read_len(b, c[u].rid);
         wlen[u] = (uint32_t)(c[u].re - c[u].rs + 1);
         live[u] = !(c[u].flags & (RCF_BANDED | RCF_ERR | RCF_QN | RCF_SCORED)) && wlen[u] <= wcap;
-        gbase[u] = (c[u].sqidx < 0 ? 0ull : ix.sop[c[u].sqidx]) + c[u].rs;
-        q[u] = ((c[u].flags & RCF_REVERSE) ? b.codes_rc : b.codes) + b.read_off[c[u].rid];
+        gbase[u] = sw_task_gbase(ix, c[u]);
+        q[u] = sw_task_query(b, c[u]);
       }
       if (!live[u]) { qlen[u] = 0; wlen[u] = 0; }
     }
@@ -1371,7 +1438,7 @@ __global__ void __launch_bounds__(64) k_sw_strip16(Batch b, DevIndex ix, MapPar 
 #pragma unroll
       for (int u = 0; u < 2; u++) {
         if (live[u]) {
-          const int best = (int)((bb >> (16 * u)) & 0xffffu);
+          const int best = (int)((bb >> (16 * u)) & 0xffffu);               // as sw_store_score
           b.rcpool[tix[u]].swscor = best;
           b.rcpool[tix[u]].flags = c[u].flags | RCF_SCORED | (best >= 65535 ? RCF_BANDED : 0u);   // ERRCODE_SWATEXCEED -> K2b
           cells += (unsigned long long)qlen[u] * wlen[u];
@@ -1389,7 +1456,7 @@ __global__ void __launch_bounds__(64) k_sw_strip(Batch b, DevIndex ix, MapPar p,
   if (nlist == 0) return;
   __shared__ uint2 tab[8];
   __shared__ int2 ring[256];
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
+  const int bias = sw_bias(p);
   sw_tab8(tab, p, bias);
   __syncthreads();
   const bool listed = b.strip_list && nlist <= b.strip_cap;
@@ -1402,19 +1469,14 @@ __global__ void __launch_bounds__(64) k_sw_strip(Batch b, DevIndex ix, MapPar p,
     const RCand c = b.rcpool[t];
     const uint32_t qlen = read_len(b, c.rid), wlen = (uint32_t)(c.re - c.rs + 1);
     if ((c.flags & (RCF_BANDED | RCF_ERR | RCF_SCORED)) || wlen > wcap) continue;     // wave-uniform
-    const uint64_t gbase = (c.sqidx < 0 ? 0ull : ix.sop[c.sqidx]) + c.rs;
-    const uint8_t *q = ((c.flags & RCF_REVERSE) ? b.codes_rc : b.codes) + b.read_off[c.rid];
+    const uint64_t gbase = sw_task_gbase(ix, c);
+    const uint8_t *q = sw_task_query(b, c);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < wlen; i += 64) win[i] = (uint8_t)ref_code(ix.packed, gbase + i);
     __threadfence();
     __syncthreads();
     const int best = sw_strip_core(q, qlen, win, wlen, bnd, wcap, tab, ring, bias, -p.gap_init, -p.gap_ext);
-    if (threadIdx.x == 0) {
-      b.rcpool[t].swscor = best;
-      b.rcpool[t].flags = c.flags | RCF_SCORED | (best >= 65535 ? RCF_BANDED : 0u);   // ERRCODE_SWATEXCEED -> K2b
-      cells += (unsigned long long)qlen * wlen;
-      ntasks_done += best < 65535 ? 1 : 0;      /* a score that left 16 bits waits for K2b */
-    }
+    if (threadIdx.x == 0) sw_store_score(b.rcpool + t, c.flags, best, qlen, wlen, cells, ntasks_done);
   }
   if (threadIdx.x == 0 && cells) { atomicAdd(b.work + WK_CELLS_FULL, cells); atomicAdd(b.work + WK_TASKS_FULL, ntasks_done); }
 }
@@ -1424,7 +1486,7 @@ __global__ void __launch_bounds__(64) k_sw_strip_raw(const uint8_t *qcodes, cons
                                                      uint32_t ntask, MapPar p, int32_t *scores, int2 *bnd_all, uint8_t *win_all, uint32_t wcap) {
   __shared__ uint2 tab[8];
   __shared__ int2 ring[256];
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
+  const int bias = sw_bias(p);
   sw_tab8(tab, p, bias);
   __syncthreads();
   int2 *bnd = bnd_all + (size_t)blockIdx.x * 2 * wcap;
@@ -1433,7 +1495,7 @@ __global__ void __launch_bounds__(64) k_sw_strip_raw(const uint8_t *qcodes, cons
     const uint32_t qlen = q_off[t + 1] - q_off[t], wlen = r_off[t + 1] - r_off[t];
     if (wlen > wcap) { if (threadIdx.x == 0) scores[t] = -1; continue; }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < wlen; i += 64) { const uint32_t cd = rcodes[r_off[t] + i] & 7; win[i] = (uint8_t)(cd == 7 ? 0 : (cd == 6 || cd == 4) ? 5 : cd); }
+    for (uint32_t i = threadIdx.x; i < wlen; i += 64) win[i] = (uint8_t)sw_code_of_byte(rcodes[r_off[t] + i]);
     __threadfence();
     __syncthreads();
     const int best = sw_strip_core(qcodes + q_off[t], qlen, win, wlen, bnd, wcap, tab, ring, bias, -p.gap_init, -p.gap_ext);
@@ -1478,7 +1540,7 @@ __global__ void __launch_bounds__(64) k_sw_strip16_raw(const uint8_t *qcodes, co
       for (uint32_t i = threadIdx.x; i < wmax; i += 64) {
         uint32_t cd[2];
 #pragma unroll
-        for (int u = 0; u < 2; u++) { const uint32_t x = i < wlen[u] ? (r[u][i] & 7u) : 5u; cd[u] = x == 7 ? 0 : ((x == 6 || x == 4) ? 5 : x); }
+        for (int u = 0; u < 2; u++) cd[u] = i < wlen[u] ? sw_code_of_byte(r[u][i]) : 5u;
         win[i] = (uint16_t)(cd[0] | (cd[1] << 8));
       }
       __threadfence();
@@ -1597,7 +1659,7 @@ __global__ void __launch_bounds__(64) k_sw_band(Batch b, DevIndex ix, MapPar p, 
   if (nlist == 0 || !b.strip_list || nlist > b.strip_cap) return;       // k_sw_scalar takes whatever is left
   __shared__ uint2 tab[8];
   __shared__ int2 ring[256];
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
+  const int bias = sw_bias(p);
   sw_tab8(tab, p, bias);
   __syncthreads();
   int2 *bnd = bnd_all + (size_t)blockIdx.x * 2 * wcap;
@@ -1613,8 +1675,8 @@ __global__ void __launch_bounds__(64) k_sw_band(Batch b, DevIndex ix, MapPar p, 
       if (threadIdx.x == 0) b.rcpool[t].flags = c.flags | RCF_ERR;
       continue;
     }
-    const uint64_t gbase = (c.sqidx < 0 ? 0ull : ix.sop[c.sqidx]) + c.rs;
-    const uint8_t *q = ((c.flags & RCF_REVERSE) ? b.codes_rc : b.codes) + b.read_off[c.rid];
+    const uint64_t gbase = sw_task_gbase(ix, c);
+    const uint8_t *q = sw_task_query(b, c);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < wlen; i += 64) win[i] = (uint8_t)ref_code(ix.packed, gbase + i);
     __threadfence();
@@ -1642,8 +1704,8 @@ __global__ void __launch_bounds__(64) k_sw_scalar(Batch b, DevIndex ix, MapPar p
     RCand c = b.rcpool[t];
     if (c.flags & (RCF_ERR | RCF_SCORED)) { if (!(c.flags & RCF_BANDED) || (c.flags & (RCF_ERR | RCF_BSCORED))) continue; }
     const uint32_t qlen = read_len(b, c.rid), wlen = (uint32_t)(c.re - c.rs + 1);
-    const uint8_t *q = ((c.flags & RCF_REVERSE) ? b.codes_rc : b.codes) + b.read_off[c.rid];
-    const uint64_t gbase = (c.sqidx < 0 ? 0ull : ix.sop[c.sqidx]) + c.rs;
+    const uint8_t *q = sw_task_query(b, c);
+    const uint64_t gbase = sw_task_gbase(ix, c);
     bool banded = (c.flags & RCF_BANDED) != 0;
     if (!banded) {
       if (wlen <= (uint32_t)SW_FULL_WMAX && qlen <= (uint32_t)full_gc) continue;   // k_sw_full did / will do it
@@ -1667,7 +1729,7 @@ __global__ void __launch_bounds__(64) k_sw_band_raw(const uint8_t *qcodes, const
                                                     uint32_t wcap) {
   __shared__ uint2 tab[8];
   __shared__ int2 ring[256];
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
+  const int bias = sw_bias(p);
   sw_tab8(tab, p, bias);
   __syncthreads();
   int2 *bnd = bnd_all + (size_t)blockIdx.x * 2 * wcap;
@@ -1704,83 +1766,6 @@ __global__ void __launch_bounds__(64) k_sw_band_scalar_raw(const uint8_t *qcodes
   if (!band_init(bd, bd4.x, bd4.y, bd4.z, bd4.w, (int)qlen, 0, (int)wlen - 1, (int)wlen))
     best = band_fast_scalar(bd, qcodes + q_off[t], packed, (uint64_t)r_off[t], M, -p.gap_init, -p.gap_ext, Hp, Ep);
   scores[t] = best;
-}
-
-// stand-alone K2a over explicit (query, window) code arrays -- parity tests of the kernel
-template <int G, int C>
-__global__ void __launch_bounds__(64) k_sw_full_raw(const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
-                                                     const uint32_t *r_off, uint32_t ntask, MapPar p, int32_t *scores) {
-  constexpr int NG = 64 / G;
-  constexpr int WMAX = SW_FULL_WMAX;
-  __shared__ uint8_t win[NG][WMAX + 8];
-  __shared__ uint2 tab[8];
-  const int lane = threadIdx.x, g = lane % G, grp = lane / G;
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
-  const int gi = -p.gap_init, ge = -p.gap_ext;
-  if (lane < 8) {
-    int rb = lane == 7 ? 0 : ((lane == 6 || lane == 4) ? 5 : lane);
-    uint32_t w[2] = {0, 0};
-    for (int qc = 0; qc < 8; qc++) {
-      int v = (rb == 5 || qc >= 4) ? 0 : ((rb == qc) ? p.match : p.mismatch);
-      w[qc >> 2] |= (uint32_t)((v + bias) & 0xff) << (8 * (qc & 3));
-    }
-    tab[lane] = make_uint2(w[0], w[1]);
-  }
-  __syncthreads();
-  const uint32_t ngroups = gridDim.x * NG;
-  for (uint32_t t0 = blockIdx.x * NG; t0 < ntask; t0 += ngroups) {
-    const uint32_t t = t0 + grp;
-    uint32_t qlen = 0, wlen = 0;
-    const uint8_t *q = qcodes, *r = rcodes;
-    bool live = false;
-    if (t < ntask) {
-      qlen = q_off[t + 1] - q_off[t]; wlen = r_off[t + 1] - r_off[t];
-      q += q_off[t]; r += r_off[t];
-      live = wlen <= (uint32_t)WMAX && qlen <= (uint32_t)(G * C);
-    }
-    if (!live) { qlen = 0; wlen = 0; }
-    for (uint32_t i = g; i < wlen; i += G) { uint32_t cd = r[i] & 7; win[grp][i] = (uint8_t)(cd == 7 ? 0 : (cd == 6 || cd == 4) ? 5 : cd); }
-    uint32_t sel[C];
-#pragma unroll
-    for (int cc = 0; cc < C; cc++) {
-      uint32_t j = (uint32_t)(g * C + cc);
-      uint32_t qc = (j < qlen) ? (q[j] & 7u) : 5u;
-      sel[cc] = 0x0c0c0c00u | qc;
-    }
-    int H[C], E[C];
-#pragma unroll
-    for (int cc = 0; cc < C; cc++) { H[cc] = 0; E[cc] = 0; }
-    int best = 0, F = 0, prev_hl = 0;
-    int nstep = (int)wlen + G - 1;
-    for (int o = 32; o > 0; o >>= 1) nstep = max(nstep, __shfl_xor(nstep, o));
-    __syncthreads();
-    for (int step = 0; step < nstep; step++) {
-      const int row = step - g;
-      const uint32_t rb = (row >= 0 && row < (int)wlen) ? win[grp][row] : 5u;
-      const uint2 tr = tab[rb];
-      int hl = shr1<G>(H[C - 1]);
-      int fin = shr1<G>(F);
-      if (g == 0) { hl = 0; fin = 0; }
-      int diag = prev_hl;
-      prev_hl = hl;
-      F = fin;
-#pragma unroll
-      for (int cc = 0; cc < C; cc++) {
-        const int w = (int)__builtin_amdgcn_perm(tr.y, tr.x, sel[cc]);
-        const int h = diag + w - bias;
-        const int hh = max(max(h, E[cc]), F);
-        best = max(best, hh);
-        diag = H[cc];
-        H[cc] = hh;
-        const int tt = hh - gi;
-        E[cc] = max(max(E[cc] - ge, tt), 0);
-        F = max(max(F - ge, tt), 0);
-      }
-    }
-    for (int o = G / 2; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
-    if (t < ntask && g == 0) scores[t] = live ? best : -1;
-    __syncthreads();
-  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1882,20 +1867,38 @@ int launch_align(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar
   return 0;
 }
 
+// The tilings of the register-tiled K2a kernels: reads of up to qmax bases (qmax <= G * C) take G lanes of C columns.
+// A new tiling is a line here and a case in sw_tiling_dispatch.
+struct SwTiling { uint32_t qmax; int G, C; };
+static const SwTiling sw_tilings[] = {{64, 4, 16}, {104, 8, 13}, {152, 8, 19}, {160, 8, 20}, {256, 16, 16}, {512, 16, 32}};
+
 int sw_full_geometry(uint32_t qmax_len, int *G, int *C) {
-  if (qmax_len <= 64) { *G = 4; *C = 16; }
-  else if (qmax_len <= 104) { *G = 8; *C = 13; }
-  else if (qmax_len <= 152) { *G = 8; *C = 19; }
-  else if (qmax_len <= 160) { *G = 8; *C = 20; }
-  else if (qmax_len <= 256) { *G = 16; *C = 16; }
-  else if (qmax_len <= 512) { *G = 16; *C = 32; }
-  else { *G = 0; *C = 0; return -1; }
-  return 0;
+  for (const SwTiling &t : sw_tilings)
+    if (qmax_len <= t.qmax) { *G = t.G; *C = t.C; return 0; }
+  *G = 0; *C = 0;
+  return -1;
+}
+
+// f(SwTile<G, C>()): the tiling as compile-time constants; false for a tiling that has no instances
+template <int TG, int TC> struct SwTile { enum : int { G = TG, C = TC }; };
+template <typename F>
+static bool sw_tiling_dispatch(int G, int C, F &&f) {
+#define SW_TILING(g, c) case (g) * 64 + (c): f(SwTile<g, c>()); return true
+  switch (G * 64 + C) {
+    SW_TILING(4, 16);
+    SW_TILING(8, 13);
+    SW_TILING(8, 19);
+    SW_TILING(8, 20);
+    SW_TILING(16, 16);
+    SW_TILING(16, 32);
+  }
+#undef SW_TILING
+  return false;
 }
 
 // the packed kernel's 16-bit lanes hold any score of a read of up to 512 bases
 static bool sw16_ok(const MapPar &p) {
-  const int bias = (p.mismatch < p.mismatch - p.match ? -p.mismatch : -(p.mismatch - p.match));
+  const int bias = sw_bias(p);
   return p.match > 0 && p.match * 512 + bias + 256 < 0x7C00 /* pk_max3 */ && bias >= 0 && p.match + bias < 256 && p.mismatch + bias >= 0 &&
          -p.gap_init >= 0 && -p.gap_init < 30000 && -p.gap_ext >= 0 && -p.gap_ext < 30000;
 }
@@ -1919,26 +1922,20 @@ int sw16_pairframe_max_steps(int match, int mismatch, int gap_init, int gap_ext,
   return sw16_pairframe_steps(match, mismatch, gap_init, gap_ext, ncols);
 }
 
-template <int G, int C>
-static void launch_sw_full_t(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t ntask_cap, uint32_t grid) {
-  const int use16 = sw16_ok(p);
-  if (use16) {
-    const int rf = sw16_frames_on();
-    hipLaunchKernelGGL((k_sw_full16<G, C, SW_SHORT_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
-    hipLaunchKernelGGL((k_sw_full16<G, C, SW_FULL_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
-  }
-  hipLaunchKernelGGL((k_sw_full<G, C>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, use16);
-}
-
 int launch_sw_full(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t qmax_len, uint32_t ntask_cap, uint32_t grid) {
   int G, C;
   if (sw_full_geometry(qmax_len, &G, &C)) return 0;    // nothing for the register-tiled kernel: k_sw_scalar takes all
-  if (G == 4) launch_sw_full_t<4, 16>(s, b, ix, p, ntask_cap, grid);
-  else if (G == 8 && C == 13) launch_sw_full_t<8, 13>(s, b, ix, p, ntask_cap, grid);
-  else if (G == 8 && C == 19) launch_sw_full_t<8, 19>(s, b, ix, p, ntask_cap, grid);
-  else if (G == 8) launch_sw_full_t<8, 20>(s, b, ix, p, ntask_cap, grid);
-  else if (C == 16) launch_sw_full_t<16, 16>(s, b, ix, p, ntask_cap, grid);
-  else launch_sw_full_t<16, 32>(s, b, ix, p, ntask_cap, grid);
+  const int use16 = sw16_ok(p);
+  const bool known = sw_tiling_dispatch(G, C, [&](auto tile) {
+    constexpr int TG = decltype(tile)::G, TC = decltype(tile)::C;
+    if (use16) {
+      const int rf = sw16_frames_on();
+      hipLaunchKernelGGL((k_sw_full16<TG, TC, SW_SHORT_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
+      hipLaunchKernelGGL((k_sw_full16<TG, TC, SW_FULL_WMAX>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, rf);
+    }
+    hipLaunchKernelGGL((k_sw_full<TG, TC>), dim3(grid), dim3(64), 0, s, b, ix, p, ntask_cap, use16);
+  });
+  if (!known) return (int)hipErrorInvalidValue;
   SMG_LAUNCH_CHECK();
   return 0;
 }
@@ -2002,13 +1999,6 @@ int launch_sw_scalar(hipStream_t s, const Batch &b, const DevIndex &ix, const Ma
   hipLaunchKernelGGL(k_sw_scalar, dim3(nthreads / 64), dim3(64), 0, s, b, ix, p, rows, rowlen, full_gc);
   SMG_LAUNCH_CHECK();
   return 0;
-}
-
-template <int G, int C>
-static void launch_sw_raw_t(hipStream_t s, const uint8_t *q, const uint32_t *qo, const uint8_t *r, const uint32_t *ro, uint32_t n,
-                            const MapPar &p, int32_t *sc, uint32_t grid, int packed16) {
-  if (packed16) hipLaunchKernelGGL((k_sw_full16_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc, sw16_frames_on());
-  else hipLaunchKernelGGL((k_sw_full_raw<G, C>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc);
 }
 
 // test entry of the candidate ranking sort (smg_wsort.hpp): one wave per array of keys
@@ -2075,12 +2065,12 @@ int launch_sw_full_raw(hipStream_t s, const uint8_t *q, const uint32_t *qo, cons
   if (packed16 && !sw16_ok(p)) return -2;
   uint32_t grid = (n + (64 / G) - 1) / (64 / G);
   if (grid > 8192) grid = 8192;
-  if (G == 4) launch_sw_raw_t<4, 16>(s, q, qo, r, ro, n, p, sc, grid, packed16);
-  else if (G == 8 && C == 13) launch_sw_raw_t<8, 13>(s, q, qo, r, ro, n, p, sc, grid, packed16);
-  else if (G == 8 && C == 19) launch_sw_raw_t<8, 19>(s, q, qo, r, ro, n, p, sc, grid, packed16);
-  else if (G == 8) launch_sw_raw_t<8, 20>(s, q, qo, r, ro, n, p, sc, grid, packed16);
-  else if (C == 16) launch_sw_raw_t<16, 16>(s, q, qo, r, ro, n, p, sc, grid, packed16);
-  else launch_sw_raw_t<16, 32>(s, q, qo, r, ro, n, p, sc, grid, packed16);
+  const bool known = sw_tiling_dispatch(G, C, [&](auto tile) {
+    constexpr int TG = decltype(tile)::G, TC = decltype(tile)::C;
+    if (packed16) hipLaunchKernelGGL((k_sw_full16_raw<TG, TC>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc, sw16_frames_on());
+    else hipLaunchKernelGGL((k_sw_full_raw<TG, TC>), dim3(grid), dim3(64), 0, s, q, qo, r, ro, n, p, sc);
+  });
+  if (!known) return (int)hipErrorInvalidValue;
   SMG_LAUNCH_CHECK();
   return 0;
 }
