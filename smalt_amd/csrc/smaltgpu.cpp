@@ -1,40 +1,22 @@
 // smaltgpu.cpp -- host side of libsmaltgpu.so: the C ABI of include/smaltgpu.h on top of the
 // gfx950 kernels.  Device memory, one HIP stream and all scratch are owned by the mapper (the
 // analogue of the reference's RMap, rmap.c:130-171, which owns every per-thread buffer).
-// There is no CPU code path: every entry point needs a HIP device.
-#include <hip/hip_runtime.h>
+// There is no CPU code path: every entry point needs a HIP device.  The stand-alone entries of single kernels (tests) are in
+// smg_entries.cpp; smg_mapper.hpp holds the mapper and the steps of a call that both files run.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-#include <mutex>
-#include <string>
 #include <thread>
-#include <vector>
-#include "../../include/smaltgpu.h"
-#include "smg_dump.hpp"
+#include "smg_mapper.hpp"
 #include "smg_indexfile.hpp"
 #include "smg_indexbuild.h"
 #include "smg_fasta.hpp"
-#include "smg_kernels.h"
-
-using namespace smg;
 
 static thread_local std::string g_err;
-static int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
+extern "C" const char *smaltgpu_last_error(void) { return g_err.c_str(); }
+extern "C" int smaltgpu_set_error(int code, const char *msg) {   // fail (smg_mapper.hpp) and the library's other translation units
+  g_err.assign(msg ? msg : "", msg ? strnlen(msg, 511) : 0);
   return code;
 }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(SMALTGPU_ENODEV, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
-extern "C" const char *smaltgpu_last_error(void) { return g_err.c_str(); }
-extern "C" int smaltgpu_set_error(int code, const char *msg) { return fail(code, "%s", msg ? msg : ""); }   // for the library's other translation units
 extern "C" int smaltgpu_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -42,21 +24,6 @@ extern "C" int smaltgpu_device_count(void) {
 }
 
 // ------------------------------------------------------------------------------------------
-struct smaltgpu_index {
-  DevIndex d;
-  int device = 0;
-  bool owns = true;
-  std::vector<uint64_t> sop;       // host copy
-  void *bufs[8] = {nullptr};
-  int nbufs = 0;
-  std::vector<std::string> names;  // set by smaltgpu_index_build (what smaltgpu_index_save writes)
-  uint32_t maxpos = 0;
-  bool built = false;
-  std::vector<const char *> name_ptrs;  // smaltgpu_index_seqnames
-  std::vector<uint32_t> packed_host;   // host copy of the packed reference, fetched on first request (smaltgpu_index_packed_host)
-  std::mutex packed_mu;
-};
-
 template <class T>
 static int upload(smaltgpu_index *ix, const T *host, size_t n, const T **dev) {
   T *p = nullptr;
@@ -351,102 +318,14 @@ extern "C" void smaltgpu_params_default(smaltgpu_params *p, const smaltgpu_index
 }
 
 // ------------------------------------------------------------------------------------------
-enum { T_ENCODE = 0, T_SEED, T_HITS, T_CANDS, T_SW_FULL, T_SW_SCALAR, T_REPLAY, T_ALIGN, T_NUM };
 static const char *const kTimerNames[T_NUM] = {"encode", "seed", "hits", "cands", "sw_full", "sw_scalar", "replay", "align"};
 extern "C" const char *smaltgpu_timer_name(int i) { return (i >= 0 && i < T_NUM) ? kTimerNames[i] : nullptr; }
 
-struct smaltgpu_mapper {
-  const smaltgpu_index *ix = nullptr;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  uint32_t max_reads = 0, max_len = 0, qmax = 0;
-  uint64_t max_bases = 0;
-  // device buffers
-  uint8_t *d_bases = nullptr, *d_quals = nullptr, *d_codes = nullptr, *d_codes_rc = nullptr;
-  uint64_t *d_off = nullptr;
-  uint32_t *d_ids = nullptr;
-  uint32_t hits_W = 0, hits_wg = 0;          // k_hits: keys per window, workgroups (0: S3 stays inside k_cands)
-  HitRun *b_hitrun = nullptr;                 // the run table (Batch::hitrun is set per call: restricted calls do not use it)                  // read ids of a round gathered from resident batches (smaltgpu_map_batch_ctx_resident)
-  Batch b;
-  // Counters of a batch, one 128-byte line each: atomics on one line are served one after the other (2 ns each), and the pool cursors,
-  // the work-queue cursors of the persistent kernels and the retry counts used to share the first line.
-  enum : size_t { CT_LINE = 128, CT_RC = 0, CT_RES = 1 * CT_LINE, CT_DSTR = 2 * CT_LINE, CT_ERR = 3 * CT_LINE, CT_NEXT = 4 * CT_LINE /* 5 lines */,
-                  CT_ALIGN_RETRY = 9 * CT_LINE, CT_CANDS_RETRY = 10 * CT_LINE, CT_HITS = 11 * CT_LINE, CT_HITS_CURSOR = 12 * CT_LINE, CT_STRIP_CURSOR = 13 * CT_LINE,
-                  CT_WORK = 14 * CT_LINE /* 32 x 8 bytes */, CT_BYTES = 16 * CT_LINE };
-  uint8_t *d_counters = nullptr;
-  double *d_logtab = nullptr; uint32_t logtab_n = 0;     // log(n), n <= max_len, for the complexity-weighted scores (SMALTGPU_FLG_CMPLXW; smg_cplx.hpp)
-  uint8_t *seed_scr = nullptr; size_t seed_bytes = 0; uint32_t seed_slots = 0;
-  uint8_t *cand_scr = nullptr; size_t cand_bytes = 0; uint32_t cand_slots = 0;
-  CandGeom cg2; uint8_t *cand_scr2 = nullptr; size_t cand_bytes2 = 0; uint32_t cand_slots2 = 0;   // second pass of the candidate stage: full-size slots
-  CandGeom cg;
-  uint8_t *cand_scr_dbg = nullptr; uint32_t cand_dbg_reads = 0;
-  int *sw_rows = nullptr; uint32_t sw_rowlen = 0, sw_threads = 0;
-  void *strip_bnd = nullptr; uint8_t *strip_win = nullptr; uint32_t strip_grid = 0;   // k_sw_strip: boundary columns + decoded window per workgroup
-  uint32_t full_grid = 8192;                          // workgroups (one wave each) of the register-tiled K2a kernels
-  uint8_t *align_scr = nullptr; size_t align_bytes = 0; uint32_t align_slots = 0;
-  uint8_t *align_scr2 = nullptr; size_t align_bytes2 = 0; uint32_t align_slots2 = 0; uint64_t dircap2 = 0;   // second K3 pass: few slots with full-size direction matrices
-  uint32_t wincap = 0, rescap_slot = 0, dstrcap_slot = 0; uint64_t dircap = 0;
-  uint32_t rescap_slot2 = 0, dstrcap_slot2 = 0;       // result slots of the second K3 pass (reads with more alignments than a first-pass slot holds)
-  // host mirrors
-  // results come back through pinned host memory: the copies are asynchronous, so the next batch can be launched
-  // behind them (smaltgpu_fetch_begin / _end)
-  template <class T> struct Pinned {
-    T *p = nullptr; size_t cap = 0;
-    int ensure(size_t n) {
-      if (n <= cap) return 0;
-      size_t c = cap ? cap : 1024;
-      while (c < n) c += c / 2 + 1;
-      T *q = nullptr;
-      if (hipHostMalloc((void **)&q, c * sizeof(T), hipHostMallocDefault) != hipSuccess) return -1;
-      if (p) (void)hipHostFree(p);
-      p = q; cap = c;
-      return 0;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    T *data() { return p; }
-    T &operator[](size_t i) { return p[i]; }
-  };
-  Pinned<ReadStat> h_stat;
-  Pinned<Result> h_res;
-  Pinned<uint8_t> h_dstr;
-  hipEvent_t ev_fetch = nullptr;
-  uint32_t fetch_n = 0; uint64_t fetch_nres = 0; bool fetch_open = false, pool_overflow = false;
-  // smaltgpu_map_batch after a pool overflow: results of the whole batch assembled from several device batches
-  std::vector<smaltgpu_result> fin_res; std::vector<uint8_t> fin_dstr; std::vector<smaltgpu_readstat> fin_stat; std::vector<uint64_t> fin_off;
-  std::vector<uint64_t> h_res_off;
-  std::vector<smaltgpu_result> o_res;
-  std::vector<smaltgpu_readstat> o_stat;
-  std::vector<uint64_t> h_off;              // read offsets of the last batch (host copy)
-  uint32_t last_n = 0;
-  MapPar last_par;
-  bool have_host_off = false;
-  int debug = 0;
-  // per-read context of rmapPair's rounds (smaltgpu_map_batch_ctx): device copies, grown on demand
-  struct DevBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n) { if (n <= cap) return 0; if (p) (void)hipFree(p); p = nullptr; cap = 0; size_t c = n + n / 2 + 256; if (hipMalloc(&p, c) != hipSuccess) return -1; cap = c; return 0; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  };
-  DevBuf cx_ivoff, cx_iv, cx_minsw, cx_prevmax, cx_fineidx, cx_finepos, cx_fineoff, cx_alloclen, cx_seedrange;
-  int host_threads = 1;                      // smaltgpu_mapper_set_host_threads
-  bool history = false;                      // serial-order mode (smaltgpu_mapper_set_history)
-  uint32_t hist_longest = 0;                 // longest read of length >= k of the run so far
-  std::vector<uint32_t> h_alloclen;
-  std::vector<uint32_t> h_ivoff, h_fineoff, h_finepos, h_fineidx;      // (the last two: host copies for smaltgpu_fine_index_batch, test entry)
-  std::vector<HitInfoHdr> h_hi;
-  bool last_fine = false;
-  uint64_t remap_batches = 0;               // device batches smaltgpu_map_batch ran to recover from pool overflows (diagnostic)
-  // host copies of what k_hits left behind (smaltgpu_hits_batch, test entry)
-  struct HitsHost { std::vector<HitInfoHdr> hi; std::vector<uint32_t> n_seeds, seed_rank, status; std::vector<SeedRec> seeds; std::vector<uint8_t> qmask;
-                    std::vector<HitRun> runs; std::vector<uint64_t> pool; } hh;
-  hipEvent_t ev[T_NUM + 1] = {nullptr};
-  double ms[T_NUM] = {0};
-  unsigned long long work[WK_NWORK] = {0};
-};
-
+// device memory of a mapper: recorded in m->owned, freed by smaltgpu_mapper_free
 template <class T>
-static int dalloc(T **p, size_t n) {
+static int dalloc(smaltgpu_mapper *m, T **p, size_t n) {
   HIPCHK(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
+  m->owned.push_back(*p);
   return 0;
 }
 
@@ -466,14 +345,13 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
   m->ix = ix; m->device = ix->device; m->max_reads = max_batch_reads; m->max_len = max_read_len;
   m->qmax = (max_read_len + 8 + 7) & ~7u;
   m->max_bases = (uint64_t)max_batch_reads * max_read_len;
-  HIPCHK(hipStreamCreate(&m->stream));
-  for (int i = 0; i <= T_NUM; i++) HIPCHK(hipEventCreate(&m->ev[i]));
+  // from here on every failure leaves through smaltgpu_mapper_free(m) at the end: each step runs only while rv is 0
+  int rv = [m]() { HIPCHK(hipStreamCreate(&m->stream)); for (int i = 0; i <= T_NUM; i++) HIPCHK(hipEventCreate(&m->ev[i])); return 0; }();
   const DevIndex &d = ix->d;
   Batch &b = m->b;
   memset(&b, 0, sizeof(b));
   b.qmax = m->qmax;
-  int rv = 0;
-#define DA(ptr, n) if (!rv) rv = dalloc(&(ptr), (size_t)(n))
+#define DA(ptr, n) if (!rv) rv = dalloc(m, &(ptr), (size_t)(n))
   DA(m->d_bases, m->max_bases + 16); DA(m->d_quals, m->max_bases + 16); DA(m->d_codes, m->max_bases + 16); DA(m->d_codes_rc, m->max_bases + 16);
   DA(m->d_off, (size_t)max_batch_reads + 1);
   DA(m->d_ids, (size_t)max_batch_reads + 1);
@@ -532,8 +410,7 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
       if (cap < (1ull << 20)) cap = 1ull << 20;                 // one read alone always fits (<= 2 x 4 x its hit-list allocation)
       b.hitpool_cap = cap;
       DA(b.hitpool, cap);
-      DA(b.hitrun, 2 * (size_t)max_batch_reads);
-      m->b_hitrun = b.hitrun;
+      DA(m->b_hitrun, 2 * (size_t)max_batch_reads);
       const char *hw = getenv("SMALTGPU_HITS_WINDOW");
       m->hits_W = hw ? (uint32_t)atoi(hw) : 1024u;       // measured (1 M reads of the bench): 512: 195 ms, 768: 124 ms, 1024: 112 ms
       if (m->hits_W < 256) m->hits_W = 256;
@@ -643,7 +520,7 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
     // tuning hook; with a few workgroups a wave meets the same read in successive iterations even on a small batch (tests/test_gpu_sw_prologue.py)
     if (const char *e = getenv("SMALTGPU_SWFULL_GRID")) { const long v = atol(e); if (v >= 1 && v <= 16384) m->full_grid = (uint32_t)v; }
     if ((uint64_t)m->strip_grid * m->wincap * 18 > (8ull << 30)) m->strip_grid = (uint32_t)((8ull << 30) / ((uint64_t)m->wincap * 18));
-    if (!rv) rv = dalloc((uint8_t **)&m->strip_bnd, (size_t)m->strip_grid * 2 * m->wincap * 8);
+    if (!rv) rv = dalloc(m, (uint8_t **)&m->strip_bnd, (size_t)m->strip_grid * 2 * m->wincap * 8);
     DA(m->strip_win, (size_t)m->strip_grid * m->wincap * 2);      // code pairs of the packed strip kernel
     m->dircap = (uint64_t)(m->qmax + 64) * (m->wincap + 8);
     m->rescap_slot = 512; m->dstrcap_slot = 512 * (m->qmax / 4 + 48);
@@ -683,16 +560,12 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
 extern "C" void smaltgpu_mapper_free(smaltgpu_mapper *m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
-  void *ps[] = {m->d_bases, m->d_quals, m->d_codes, m->d_codes_rc, m->d_off, m->d_ids, m->b.hi, m->b.seeds, m->b.qmask, m->b.ch, m->b.ctl,
-                m->b.stat, m->b.align_retry, m->b.cands_retry, m->d_logtab, m->b.hitpool, m->b_hitrun, m->b.rcpool, m->b.long_list, m->b.strip_list, m->strip_bnd, m->strip_win, m->b.respool, m->b.dstrpool, m->d_counters, m->seed_scr, m->cand_scr, m->cand_scr2, m->cand_scr_dbg,
-                m->sw_rows, m->align_scr, m->align_scr2};
-  for (void *p : ps) if (p) (void)hipFree(p);
-  m->h_stat.release(); m->h_res.release(); m->h_dstr.release();
-  m->cx_ivoff.release(); m->cx_iv.release(); m->cx_minsw.release(); m->cx_prevmax.release(); m->cx_fineidx.release(); m->cx_finepos.release(); m->cx_fineoff.release(); m->cx_alloclen.release(); m->cx_seedrange.release();
+  for (void *p : m->owned) (void)hipFree(p);
+  if (m->cand_scr_dbg) (void)hipFree(m->cand_scr_dbg);
   if (m->ev_fetch) (void)hipEventDestroy(m->ev_fetch);
   for (int i = 0; i <= T_NUM; i++) if (m->ev[i]) (void)hipEventDestroy(m->ev[i]);
   if (m->stream) (void)hipStreamDestroy(m->stream);
-  delete m;
+  delete m;      // the context buffers and the pinned host buffers release themselves
 }
 
 extern "C" int smaltgpu_set_debug(smaltgpu_mapper *m, int level) {
@@ -701,7 +574,7 @@ extern "C" int smaltgpu_set_debug(smaltgpu_mapper *m, int level) {
   return SMALTGPU_OK;
 }
 
-static MapPar to_par(const smaltgpu_params *p) {
+MapPar to_par(const smaltgpu_params *p) {
   MapPar q;
   q.cov_frac = p->min_cover_frac > 0.0 ? p->min_cover_frac : 0.0;
   q.ncut = p->ktuple_maxhit; q.min_cover = p->min_cover; q.min_swatscor = p->min_swatscor; q.below_max = p->min_swatscor_below_max;
@@ -710,7 +583,7 @@ static MapPar to_par(const smaltgpu_params *p) {
   return q;
 }
 
-static int check_par(const smaltgpu_mapper *m, const smaltgpu_params *p) {
+int check_par(const smaltgpu_mapper *m, const smaltgpu_params *p) {
   if (p->match < 1 || p->mismatch >= 0 || p->gap_init >= 0 || p->gap_ext >= 0 || p->match > 15 || p->mismatch < -100)
     return fail(SMALTGPU_EARG, "unsupported penalties");
   if (p->min_swatscor < 1) return fail(SMALTGPU_EARG, "min_swatscor must be >= 1 (alignment.c:1569)");
@@ -719,27 +592,38 @@ static int check_par(const smaltgpu_mapper *m, const smaltgpu_params *p) {
   return 0;
 }
 
+// Begin a call on the mapper's batch: the per-call fields of Batch from the round's context (null: a plain call), the mapper's
+// record of the call and zeroed counters.  run_pipeline and the entries of smg_entries.cpp that run a part of it start here.
+// fetch_open is left alone: a fetch of the previous batch may be open while the next batch is launched.
+int begin_call(smaltgpu_mapper *m, const uint8_t *d_quals, const uint64_t *d_off, uint32_t n, const smaltgpu_params *par, const CtxDev *cx,
+               bool totals_only, MapPar *p) {
+  static const CtxDev plain = {};
+  if (!cx) cx = &plain;
+  Batch &b = m->b;
+  *p = to_par(par);
+  b.iv_off = cx->iv_off; b.iv = cx->iv; b.min_sw = cx->min_sw; b.prevmax = cx->prevmax;
+  b.fine_idx = cx->fine_idx; b.fine_pos = cx->fine_pos; b.fine_off = cx->fine_off;
+  b.alloc_len = cx->alloc_len; b.seed_range = cx->seed_range;
+  b.totals_only = totals_only ? 1u : 0u; b.raw_results = cx->raw;
+  // S3 ahead of the candidate stage (plain calls of short-read mappers; restricted calls keep it inside k_cands)
+  b.hitrun = m->hits_W && !b.iv_off && !totals_only ? m->b_hitrun : nullptr;
+  if (b.fine_idx) p->flags |= FLG_NOSHRTINFO;            // initRMAPINFO, not the short form (rmap.c:2024)
+  m->last_fine = b.fine_idx != nullptr;
+  m->last_par = *p; m->last_n = n;
+  b.nreads = n; b.codes = m->d_codes; b.codes_rc = m->d_codes_rc; b.qual = d_quals; b.read_off = d_off;
+  HIPCHK(hipMemsetAsync(m->d_counters, 0, smaltgpu_mapper::CT_BYTES, m->stream));
+  return 0;
+}
+
 // the device pipeline over reads already in HBM
 // cx: the per-read context of one of rmapPair's rounds, already on the device (upload_ctx), or null
-struct CtxDev { const uint32_t *iv_off; const IvRec *iv; const int32_t *min_sw, *prevmax; uint32_t *fine_idx, *fine_pos; const uint32_t *fine_off, *alloc_len, *seed_range; uint32_t raw; };
-
 static int run_pipeline(smaltgpu_mapper *m, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_off, uint32_t n,
                         const smaltgpu_params *par, const CtxDev *cx = nullptr, bool seed_only = false) {
   Batch &b = m->b;
   const DevIndex &d = m->ix->d;
-  MapPar p = to_par(par);
-  b.iv_off = cx ? cx->iv_off : nullptr; b.iv = cx ? cx->iv : nullptr; b.min_sw = cx ? cx->min_sw : nullptr; b.prevmax = cx ? cx->prevmax : nullptr;
-  b.fine_idx = cx ? cx->fine_idx : nullptr; b.fine_pos = cx ? cx->fine_pos : nullptr; b.fine_off = cx ? cx->fine_off : nullptr;
-  b.alloc_len = cx ? cx->alloc_len : nullptr;
-  b.seed_range = cx ? cx->seed_range : nullptr;
-  b.totals_only = seed_only ? 1u : 0u;
-  b.raw_results = cx ? cx->raw : 0u;
-  if (b.fine_idx) p.flags |= FLG_NOSHRTINFO;            // initRMAPINFO, not the short form (rmap.c:2024)
-  m->last_fine = b.fine_idx != nullptr;
-  m->last_par = p; m->last_n = n;
-  b.nreads = n; b.codes = m->d_codes; b.codes_rc = m->d_codes_rc; b.qual = d_quals; b.read_off = d_off;
   hipStream_t s = m->stream;
-  HIPCHK(hipMemsetAsync(m->d_counters, 0, smaltgpu_mapper::CT_BYTES, s));
+  MapPar p;
+  TRY(begin_call(m, d_quals, d_off, n, par, cx, seed_only, &p));
   int rv = 0;
   const bool seqbyseq = (p.flags & FLG_SEQBYSEQ) != 0;
   const uint32_t ngrp = seqbyseq ? (uint32_t)d.nseq : 1u;
@@ -765,10 +649,7 @@ static int run_pipeline(smaltgpu_mapper *m, const uint8_t *d_bases, const uint8_
   HIPCHK(hipEventRecord(m->ev[T_SEED], s));
   if (!rv) rv = launch_seed(s, b, d, p, m->seed_scr, m->seed_bytes, m->seed_slots);
   HIPCHK(hipEventRecord(m->ev[T_HITS], s));
-  // S3 ahead of the candidate stage (plain calls of short-read mappers; restricted calls keep it inside k_cands)
-  const bool split_hits = m->hits_W && m->b_hitrun && !b.iv_off && !seed_only;
-  b.hitrun = split_hits ? m->b_hitrun : nullptr;
-  if (!rv && split_hits) rv = launch_hits(s, b, d, p, m->hits_W, m->cg.tab, m->hits_wg);
+  if (!rv && b.hitrun) rv = launch_hits(s, b, d, p, m->hits_W, m->cg.tab, m->hits_wg);
   HIPCHK(hipEventRecord(m->ev[T_CANDS], s));
   if (seed_only) {
     for (int i = T_CANDS + 1; i <= T_NUM; i++) HIPCHK(hipEventRecord(m->ev[i], s));
@@ -812,6 +693,11 @@ extern "C" int smaltgpu_map_batch_device(smaltgpu_mapper *m, const uint8_t *d_ba
   return run_pipeline(m, d_bases, d_quals, d_read_off, nreads, par);
 }
 
+// the stage times of the last call, once its stream has been waited for
+static void read_timers(smaltgpu_mapper *m) {
+  for (int i = 0; i < T_NUM; i++) { float f = 0; (void)hipEventElapsedTime(&f, m->ev[i], m->ev[i + 1]); m->ms[i] = f; }
+}
+
 // Results in two steps so that a caller can keep the device busy: _begin waits for the batch, reads the pool counters and
 // enqueues the copies to pinned host memory; the next batch may be launched right behind them (same stream: the copies
 // finish first); _end waits for the copies and puts the results in read order.
@@ -827,7 +713,7 @@ extern "C" int smaltgpu_fetch_begin(smaltgpu_mapper *m) {
   const uint32_t rc_count = *(uint32_t *)(ctr + smaltgpu_mapper::CT_RC);
   const uint64_t nres = *(unsigned long long *)(ctr + smaltgpu_mapper::CT_RES), ndstr = *(unsigned long long *)(ctr + smaltgpu_mapper::CT_DSTR);
   memcpy(m->work, ctr + smaltgpu_mapper::CT_WORK, sizeof(m->work));
-  for (int i = 0; i < T_NUM; i++) { float f = 0; (void)hipEventElapsedTime(&f, m->ev[i], m->ev[i + 1]); m->ms[i] = f; }
+  read_timers(m);
   m->fetch_open = false;
   // A pool that overflowed leaves SMALTGPU_ECAP in the stat of every read that did not fit (their results are dropped on the
   // device); all other reads are complete.  smaltgpu_fetch_end reports the code, smaltgpu_map_batch re-maps those reads.
@@ -904,7 +790,7 @@ extern "C" int smaltgpu_fetch_results(smaltgpu_mapper *m, smaltgpu_batch_out *ou
 }
 
 // the context of a round to the device; fills cd
-static int upload_ctx(smaltgpu_mapper *m, const smaltgpu_callctx *ctx, uint32_t n, CtxDev *cd) {
+int upload_ctx(smaltgpu_mapper *m, const smaltgpu_callctx *ctx, uint32_t n, CtxDev *cd) {
   memset(cd, 0, sizeof(*cd));
   hipStream_t s = m->stream;
   const DevIndex &d = m->ix->d;
@@ -929,50 +815,37 @@ static int upload_ctx(smaltgpu_mapper *m, const smaltgpu_callctx *ctx, uint32_t 
       if (m->h_fineoff[i] + npos > 0xFFFFFFF0ull) return fail(SMALTGPU_EARG, "interval windows too large");
       m->h_fineoff[i + 1] = (uint32_t)(m->h_fineoff[i] + npos);
     }
-    if (m->cx_ivoff.ensure(((size_t)n + 1) * 4) || m->cx_iv.ensure((size_t)(niv ? niv : 1) * sizeof(IvRec))) return fail(SMALTGPU_ENOMEM, "device memory");
+    TRY(m->cx_ivoff.ensure((size_t)n + 1)); TRY(m->cx_iv.ensure((size_t)(niv ? niv : 1)));
     HIPCHK(hipMemcpyAsync(m->cx_ivoff.p, m->h_ivoff.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
     static_assert(sizeof(IvRec) == sizeof(smaltgpu_interval), "interval layout");
     if (niv) HIPCHK(hipMemcpyAsync(m->cx_iv.p, ctx->iv + i0, (size_t)niv * sizeof(IvRec), hipMemcpyHostToDevice, s));
-    cd->iv_off = (const uint32_t *)m->cx_ivoff.p; cd->iv = (const IvRec *)m->cx_iv.p;
+    cd->iv_off = m->cx_ivoff.p; cd->iv = m->cx_iv.p;
     if (ctx->fine_index) {
       if (d.totlen + 1 > 0xFFFFFFFFull) return fail(SMALTGPU_EARG, "on-the-fly index: reference longer than 2^32 - 1 bases (rmap.c:1537-1541 would raise the stride)");
-      if (m->cx_fineidx.ensure((size_t)n * FINE_IDX_STRIDE * 4) || m->cx_finepos.ensure(((size_t)m->h_fineoff[n] + 1) * 4) || m->cx_fineoff.ensure(((size_t)n + 1) * 4))
-        return fail(SMALTGPU_ENOMEM, "device memory");
+      TRY(m->cx_fineidx.ensure((size_t)n * FINE_IDX_STRIDE)); TRY(m->cx_finepos.ensure((size_t)m->h_fineoff[n] + 1)); TRY(m->cx_fineoff.ensure((size_t)n + 1));
       HIPCHK(hipMemcpyAsync(m->cx_fineoff.p, m->h_fineoff.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
-      cd->fine_idx = (uint32_t *)m->cx_fineidx.p; cd->fine_pos = (uint32_t *)m->cx_finepos.p; cd->fine_off = (const uint32_t *)m->cx_fineoff.p;
+      cd->fine_idx = m->cx_fineidx.p; cd->fine_pos = m->cx_finepos.p; cd->fine_off = m->cx_fineoff.p;
     }
   }
   if (ctx->min_swatscor) {
     // 0 is legal here: rmapPair passes the first mate's second-best score, which is 0 when there is none (rmap.c:2003-2031);
     // the threshold block of mapSingleRead then raises it to the best first-pass score (rmap.c:1385-1393)
     for (uint32_t i = 0; i < n; i++) if (ctx->min_swatscor[i] < 0) return fail(SMALTGPU_EARG, "negative min_swatscor");
-    if (m->cx_minsw.ensure((size_t)(n ? n : 1) * 4)) return fail(SMALTGPU_ENOMEM, "device memory");
-    if (n) HIPCHK(hipMemcpyAsync(m->cx_minsw.p, ctx->min_swatscor, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    cd->min_sw = (const int32_t *)m->cx_minsw.p;
+    TRY(upload_per_read(m, m->cx_minsw, ctx->min_swatscor, n, 1, &cd->min_sw));
   }
-  if (ctx->prev_max) {
-    if (m->cx_prevmax.ensure((size_t)(n ? n : 1) * 8)) return fail(SMALTGPU_ENOMEM, "device memory");
-    if (n) HIPCHK(hipMemcpyAsync(m->cx_prevmax.p, ctx->prev_max, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    cd->prevmax = (const int32_t *)m->cx_prevmax.p;
-  }
+  if (ctx->prev_max) TRY(upload_per_read(m, m->cx_prevmax, ctx->prev_max, n, 2, &cd->prevmax));
   cd->raw = ctx->raw_alignments ? 1u : 0u;
   if (ctx->hitlist_len) {
     for (uint32_t i = 0; i < n; i++) if (ctx->hitlist_len[i] > m->max_len) return fail(SMALTGPU_EARG, "hitlist_len of read %u exceeds the mapper's max_read_len", i);
-    if (m->cx_alloclen.ensure((size_t)(n ? n : 1) * 4)) return fail(SMALTGPU_ENOMEM, "device memory");
-    if (n) HIPCHK(hipMemcpyAsync(m->cx_alloclen.p, ctx->hitlist_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    cd->alloc_len = (const uint32_t *)m->cx_alloclen.p;
+    TRY(upload_per_read(m, m->cx_alloclen, ctx->hitlist_len, n, 1, &cd->alloc_len));
   }
-  if (ctx->seed_range) {
-    if (m->cx_seedrange.ensure((size_t)(n ? n : 1) * 8)) return fail(SMALTGPU_ENOMEM, "device memory");
-    if (n) HIPCHK(hipMemcpyAsync(m->cx_seedrange.p, ctx->seed_range, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    cd->seed_range = (const uint32_t *)m->cx_seedrange.p;
-  }
+  if (ctx->seed_range) TRY(upload_per_read(m, m->cx_seedrange, ctx->seed_range, n, 2, &cd->seed_range));
   return SMALTGPU_OK;
 }
 
-// one device batch over reads in host memory: bases/quals + read_off[0..n]; ctx (may be null) is indexed like the reads
-static int map_range(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
-                     const smaltgpu_params *par, smaltgpu_batch_out *out, const smaltgpu_callctx *ctx = nullptr, bool seed_only = false) {
+// Reads in host memory onto the device: the offsets rebased to 0 (h_off, d_off) with every read checked against max_read_len,
+// bases and qualities behind them on the mapper's stream.  For map_range and for the entries that take reads from the host.
+int stage_reads(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads) {
   const uint64_t total = read_off[nreads] - read_off[0];
   m->h_off.resize((size_t)nreads + 1);
   for (uint32_t i = 0; i <= nreads; i++) {
@@ -980,13 +853,20 @@ static int map_range(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *qu
     if (i && m->h_off[i] - m->h_off[i - 1] > m->max_len) return fail(SMALTGPU_EARG, "read %u is longer than the mapper's max_read_len", i - 1);
   }
   HIPCHK(hipSetDevice(m->device));
-  HIPCHK(hipMemcpyAsync(m->d_bases, bases + read_off[0], total, hipMemcpyHostToDevice, m->stream));
-  if (quals) HIPCHK(hipMemcpyAsync(m->d_quals, quals + read_off[0], total, hipMemcpyHostToDevice, m->stream));
+  if (total) HIPCHK(hipMemcpyAsync(m->d_bases, bases + read_off[0], total, hipMemcpyHostToDevice, m->stream));
+  if (quals && total) HIPCHK(hipMemcpyAsync(m->d_quals, quals + read_off[0], total, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipMemcpyAsync(m->d_off, m->h_off.data(), ((size_t)nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
-  CtxDev cd;
-  if (ctx) { const int cr = upload_ctx(m, ctx, nreads, &cd); if (cr) return cr; }
-  const int rv = run_pipeline(m, m->d_bases, quals ? m->d_quals : nullptr, m->d_off, nreads, par, ctx ? &cd : nullptr, seed_only);
   m->have_host_off = true;
+  return SMALTGPU_OK;
+}
+
+// one device batch over reads in host memory: bases/quals + read_off[0..n]; ctx (may be null) is indexed like the reads
+static int map_range(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
+                     const smaltgpu_params *par, smaltgpu_batch_out *out, const smaltgpu_callctx *ctx = nullptr, bool seed_only = false) {
+  TRY(stage_reads(m, bases, quals, read_off, nreads));
+  CtxDev cd;
+  if (ctx) TRY(upload_ctx(m, ctx, nreads, &cd));
+  const int rv = run_pipeline(m, m->d_bases, quals ? m->d_quals : nullptr, m->d_off, nreads, par, ctx ? &cd : nullptr, seed_only);
   if (rv || seed_only) return rv;
   return smaltgpu_fetch_results(m, out);
 }
@@ -1111,6 +991,17 @@ extern "C" int smaltgpu_mapper_capacity(const smaltgpu_mapper *m, uint32_t *max_
   return SMALTGPU_OK;
 }
 
+// the hit totals of the seeding-only call that was just launched: both strands of every read
+static int hit_totals_fetch(smaltgpu_mapper *m, uint32_t nreads, uint32_t *nhits) {
+  m->h_hi.resize(2 * (size_t)nreads + 1);
+  if (nreads) HIPCHK(hipMemcpyAsync(m->h_hi.data(), m->b.hi, 2 * (size_t)nreads * sizeof(HitInfoHdr), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  read_timers(m);      // seeding only: the later stages read 0
+  memset(m->work, 0, sizeof(m->work));
+  for (uint32_t i = 0; i < nreads; i++) nhits[i] = m->h_hi[2 * (size_t)i].nhit_cut + m->h_hi[2 * (size_t)i + 1].nhit_cut;
+  return SMALTGPU_OK;
+}
+
 extern "C" int smaltgpu_hit_totals(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
                                     const smaltgpu_params *par, uint32_t *nhits) {
   if (!m || !bases || !read_off || !par || !nhits) return fail(SMALTGPU_EARG, "null argument");
@@ -1119,14 +1010,7 @@ extern "C" int smaltgpu_hit_totals(smaltgpu_mapper *m, const uint8_t *bases, con
   int rv = check_par(m, par);
   if (rv) return rv;
   rv = map_range(m, bases, quals, read_off, nreads, par, nullptr, nullptr, true);       // encode + seeding (S1, S2) only
-  if (rv) return rv;
-  m->h_hi.resize(2 * (size_t)nreads + 1);
-  if (nreads) HIPCHK(hipMemcpyAsync(m->h_hi.data(), m->b.hi, 2 * (size_t)nreads * sizeof(HitInfoHdr), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  for (int i = 0; i < T_NUM; i++) { float f = 0; (void)hipEventElapsedTime(&f, m->ev[i], m->ev[i + 1]); m->ms[i] = f; }      // seeding only: the later stages read 0
-  memset(m->work, 0, sizeof(m->work));
-  for (uint32_t i = 0; i < nreads; i++) nhits[i] = m->h_hi[2 * (size_t)i].nhit_cut + m->h_hi[2 * (size_t)i + 1].nhit_cut;
-  return SMALTGPU_OK;
+  return rv ? rv : hit_totals_fetch(m, nreads, nhits);
 }
 
 extern "C" int smaltgpu_map_batch_ctx(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
@@ -1171,7 +1055,7 @@ extern "C" int smaltgpu_mapper_set_history(smaltgpu_mapper *m, int on) {
 
 // ---- rounds over batches that are resident in HBM (reads and mates of a block of pairs): the round's reads are gathered on the
 // device; only the offsets (lengths) are needed on the host ----
-static int gather_round(smaltgpu_mapper *m, const smaltgpu_resident_reads *src, const uint32_t *ids, uint32_t nreads, bool *with_quals) {
+int gather_round(smaltgpu_mapper *m, const smaltgpu_resident_reads *src, const uint32_t *ids, uint32_t nreads, bool *with_quals) {
   m->h_off.resize((size_t)nreads + 1);
   uint64_t tot = 0;
   for (uint32_t i = 0; i < nreads; i++) {
@@ -1204,7 +1088,7 @@ extern "C" int smaltgpu_map_batch_ctx_resident(smaltgpu_mapper *m, const smaltgp
   bool wq = false;
   if ((rv = gather_round(m, src, ids, nreads, &wq))) return rv;
   CtxDev cd;
-  if (ctx) { const int cr = upload_ctx(m, ctx, nreads, &cd); if (cr) return cr; }
+  if (ctx) TRY(upload_ctx(m, ctx, nreads, &cd));
   rv = run_pipeline(m, m->d_bases, wq ? m->d_quals : nullptr, m->d_off, nreads, par, ctx ? &cd : nullptr, false);
   m->have_host_off = true;
   if (!rv) rv = smaltgpu_fetch_results(m, out);
@@ -1229,14 +1113,7 @@ extern "C" int smaltgpu_hit_totals_resident(smaltgpu_mapper *m, const smaltgpu_r
   bool wq = false;
   if ((rv = gather_round(m, src, ids, nreads, &wq))) return rv;
   rv = run_pipeline(m, m->d_bases, wq ? m->d_quals : nullptr, m->d_off, nreads, par, nullptr, true);
-  if (rv) return rv;
-  m->h_hi.resize(2 * (size_t)nreads + 1);
-  if (nreads) HIPCHK(hipMemcpyAsync(m->h_hi.data(), m->b.hi, 2 * (size_t)nreads * sizeof(HitInfoHdr), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  for (int i = 0; i < T_NUM; i++) { float f = 0; (void)hipEventElapsedTime(&f, m->ev[i], m->ev[i + 1]); m->ms[i] = f; }      // seeding only: the later stages read 0
-  memset(m->work, 0, sizeof(m->work));
-  for (uint32_t i = 0; i < nreads; i++) nhits[i] = m->h_hi[2 * (size_t)i].nhit_cut + m->h_hi[2 * (size_t)i + 1].nhit_cut;
-  return SMALTGPU_OK;
+  return rv ? rv : hit_totals_fetch(m, nreads, nhits);
 }
 
 extern "C" int smaltgpu_timers(const smaltgpu_mapper *m, double *ms, uint64_t *work, int n) {
@@ -1244,481 +1121,4 @@ extern "C" int smaltgpu_timers(const smaltgpu_mapper *m, double *ms, uint64_t *w
   for (int i = 0; i < n && i < T_NUM; i++) if (ms) ms[i] = m->ms[i];
   for (int i = 0; i < n && i < WK_NWORK; i++) if (work) work[i] = m->work[i];
   return T_NUM;
-}
-
-// ------------------------------------------------------------------------------------------
-template <class T>
-static int fetch(std::vector<T> &v, const T *dev, size_t n) {
-  v.resize(n ? n : 1);
-  if (n) HIPCHK(hipMemcpy(v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-extern "C" long smaltgpu_dump_read(smaltgpu_mapper *m, uint32_t i, const char *name, char *buf, size_t bufsiz) {
-  if (!m) return fail(SMALTGPU_EARG, "null mapper");
-  if (!m->debug || !m->cand_scr_dbg) return fail(SMALTGPU_EARG, "smaltgpu_set_debug(m, 1) must precede the batch");
-  if (i >= m->last_n || !m->have_host_off) return fail(SMALTGPU_EARG, "read index out of range");
-  HIPCHK(hipSetDevice(m->device));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  const Batch &b = m->b;
-  const DevIndex &d = m->ix->d;
-  DumpView v;
-  std::vector<HitInfoHdr> hi; std::vector<SeedRec> seeds; std::vector<uint8_t> qmask;
-  std::vector<CandHdr> ch; std::vector<ReadCtl> ctl; std::vector<ReadStat> st;
-  std::vector<uint8_t> slot;
-  if (fetch(hi, b.hi + 2 * (size_t)i, 2) || fetch(seeds, b.seeds + 2 * (size_t)i * m->qmax, 2 * (size_t)m->qmax) ||
-      fetch(qmask, b.qmask + 2 * (size_t)i * m->qmax, 2 * (size_t)m->qmax) || fetch(ch, b.ch + i, 1) || fetch(ctl, b.ctl + i, 1) ||
-      fetch(st, b.stat + i, 1) || fetch(slot, m->cand_scr_dbg + m->cand_bytes * i, m->cand_bytes)) return SMALTGPU_ENODEV;
-  const uint32_t ngrp = (m->last_par.flags & FLG_SEQBYSEQ) ? (uint32_t)d.nseq : 1u;
-  const int dk = m->last_fine ? (int)FINE_K : d.k, dsx = m->last_fine ? (int)FINE_S : d.s;
-  const bool v2 = cands_v2_applicable(m->last_par, dk, dsx, (uint32_t)(m->h_off[i + 1] - m->h_off[i]), b.iv_off != nullptr);
-  CandScratch cx = cand_scratch_carve(slot.data(), m->qmax, dsx, m->cg.hcap, ngrp, m->cg.segcap, m->cg.candcap);
-  CandsV2Scratch c2 = cands_v2_carve(nullptr, 0, slot.data(), m->qmax, dsx, m->cg.hcap_strand, ngrp, m->cg.candcap, true);
-  std::vector<RCand> rc; std::vector<Result> res; std::vector<uint8_t> dstr;
-  if (fetch(rc, b.rcpool + ch[0].rc_off, ch[0].n_sort) || fetch(res, b.respool + st[0].res_off, st[0].nres)) return SMALTGPU_ENODEV;
-  size_t nd = 0;
-  for (uint32_t j = 0; j < st[0].nres; j++) { size_t e = (size_t)res[j].stroffs + res[j].strlen; if (e > nd) nd = e; }
-  if (fetch(dstr, b.dstrpool + st[0].dstr_off, nd)) return SMALTGPU_ENODEV;
-  v.qlen = (uint32_t)(m->h_off[i + 1] - m->h_off[i]); v.qmax = m->qmax; v.k = dk;
-  for (int s2 = 0; s2 < 2; s2++) { v.hi[s2] = hi[s2]; v.seeds[s2] = seeds.data() + (size_t)s2 * m->qmax; v.qmask[s2] = qmask.data() + (size_t)s2 * m->qmax; }
-  v.ch = ch[0]; v.rc = rc.data(); v.ctl = ctl[0]; v.st = st[0]; v.res = res.data(); v.dstr = dstr.data(); v.ngrp = ngrp;
-  std::vector<SegCand> crec;
-  if (v2) { cands_v2_records(crec, c2, ch[0].ncand <= m->cg.candcap ? ch[0].ncand : 0, m->qmax > 255); v.cand = crec.data(); v.sort_idx = c2.sort_idx; v.sort_keys = c2.sort_keys; v.hitwords = c2.dbg_words; v.grp_first = c2.dbg_first; v.grp_cnt = c2.dbg_cnt; }
-  else { v.cand = cx.cand; v.sort_idx = cx.sort_idx; v.sort_keys = cx.sort_keys; v.hitwords = cx.keys; v.grp_first = cx.grp_first; v.grp_cnt = cx.grp_cnt; }
-  std::string o;
-  dump_read(o, v, i, name, m->debug >= 2);
-  if (buf && bufsiz) { size_t c = o.size() < bufsiz - 1 ? o.size() : bufsiz - 1; memcpy(buf, o.data(), c); buf[c] = 0; }
-  return (long)o.size();
-}
-
-extern "C" int smaltgpu_sw_full_batch(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
-                                       const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, int32_t *scores, int packed16) {
-  if (!m || !qcodes || !q_off || !rcodes || !r_off || !par || !scores) return fail(SMALTGPU_EARG, "null argument");
-  HIPCHK(hipSetDevice(m->device));
-  uint8_t *dq = nullptr, *dr = nullptr; uint32_t *dqo = nullptr, *dro = nullptr; int32_t *dsc = nullptr;
-  uint32_t qmaxlen = 0;
-  for (uint32_t t = 0; t < ntask; t++) { uint32_t l = q_off[t + 1] - q_off[t]; if (l > qmaxlen) qmaxlen = l; }
-  int rv = 0;
-  if (dalloc(&dq, q_off[ntask] + 16) || dalloc(&dr, r_off[ntask] + 16) || dalloc(&dqo, (size_t)ntask + 1) || dalloc(&dro, (size_t)ntask + 1) || dalloc(&dsc, ntask)) rv = SMALTGPU_ENOMEM;
-  if (!rv) {
-    (void)hipMemcpy(dq, qcodes, q_off[ntask], hipMemcpyHostToDevice);
-    (void)hipMemcpy(dr, rcodes, r_off[ntask], hipMemcpyHostToDevice);
-    (void)hipMemcpy(dqo, q_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dro, r_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
-    uint32_t rmaxlen = 0;
-    for (uint32_t t = 0; t < ntask; t++) { uint32_t l = r_off[t + 1] - r_off[t]; if (l > rmaxlen) rmaxlen = l; }
-    int lr;
-    if (!packed16 && (qmaxlen > 512 || rmaxlen > (uint32_t)SW_FULL_WMAX))     // beyond the register tiling: the strip kernel (windows up to the mapper's capacity)
-      lr = launch_sw_strip_raw(m->stream, dq, dqo, dr, dro, ntask, to_par(par), dsc, m->strip_bnd, m->strip_win, m->wincap, m->strip_grid);
-    else if (packed16 && (qmaxlen > 512 || rmaxlen > (uint32_t)SW_FULL_WMAX))                         // ... and its packed form, two tasks per wave
-      lr = launch_sw_strip16_raw(m->stream, dq, dqo, dr, dro, ntask, to_par(par), dsc, m->strip_bnd, m->strip_win, m->wincap, m->strip_grid, qmaxlen);
-    else lr = launch_sw_full_raw(m->stream, dq, dqo, dr, dro, ntask, to_par(par), dsc, qmaxlen, packed16);
-    if (lr) rv = fail(SMALTGPU_EARG, lr == -2 ? "scores do not fit the packed 16-bit kernel" : "query longer than the register-tiled kernel supports");
-    else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
-    else (void)hipMemcpy(scores, dsc, (size_t)ntask * 4, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(dq); (void)hipFree(dr); (void)hipFree(dqo); (void)hipFree(dro); (void)hipFree(dsc);
-  return rv;
-}
-
-extern "C" int smaltgpu_sw_band_batch(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
-                                       const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, const int32_t *band, int form,
-                                       int32_t *scores, int32_t *status) {
-  if (!m || !qcodes || !q_off || !rcodes || !r_off || !par || !band || !scores || !status) return fail(SMALTGPU_EARG, "null argument");
-  if (form != 0 && form != 1) return fail(SMALTGPU_EARG, "unknown form");
-  uint32_t qmaxlen = 0, rmaxlen = 0;
-  for (uint32_t t = 0; t < ntask; t++) {
-    const uint32_t ql = q_off[t + 1] - q_off[t], wl = r_off[t + 1] - r_off[t];
-    if (q_off[t + 1] <= q_off[t] || r_off[t + 1] <= r_off[t]) return fail(SMALTGPU_EARG, "empty read or window");
-    if (form == 0 && wl > m->wincap) return fail(SMALTGPU_EARG, "window above the mapper's capacity");
-    if (ql > qmaxlen) qmaxlen = ql;
-    if (wl > rmaxlen) rmaxlen = wl;
-    Band bd;
-    status[t] = band_init(bd, band[4 * t], band[4 * t + 1], band[4 * t + 2], band[4 * t + 3], (int)ql, 0, (int)wl - 1, (int)wl) ? 1 : 0;
-  }
-  // the windows back to back in the index's layout: 10 codes per word, the first in bits 29..27
-  const size_t nbase = r_off[ntask];
-  std::vector<uint32_t> packed(nbase / 10 + 2, 0u);
-  for (size_t o = 0; o < nbase; o++) packed[o / 10] |= (uint32_t)(rcodes[o] & 7u) << (3 * (9 - (uint32_t)(o % 10)));
-  HIPCHK(hipSetDevice(m->device));
-  uint8_t *dq = nullptr; uint32_t *dp = nullptr, *dqo = nullptr, *dro = nullptr; int32_t *dsc = nullptr, *dbd = nullptr; int *drows = nullptr;
-  const uint32_t rowlen = qmaxlen + rmaxlen + 2;      // band_fast_scalar looks one row past a band that has left the read
-  const size_t nrows = form == 1 ? (size_t)((ntask + 63) / 64) * 64 * 2 * rowlen : 1;
-  int rv = 0;
-  if (dalloc(&dq, q_off[ntask] + 16) || dalloc(&dp, packed.size()) || dalloc(&dqo, (size_t)ntask + 1) || dalloc(&dro, (size_t)ntask + 1) ||
-      dalloc(&dsc, (size_t)ntask + 1) || dalloc(&dbd, 4 * (size_t)ntask + 4) || dalloc(&drows, nrows)) rv = SMALTGPU_ENOMEM;
-  if (!rv) {
-    (void)hipMemcpy(dq, qcodes, q_off[ntask], hipMemcpyHostToDevice);
-    (void)hipMemcpy(dp, packed.data(), packed.size() * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dqo, q_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dro, r_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dbd, band, (size_t)ntask * 16, hipMemcpyHostToDevice);
-    (void)hipMemset(drows, 0, nrows * sizeof(int));
-    const int lr = form == 0 ? launch_sw_band_raw(m->stream, dq, dqo, dp, dro, ntask, to_par(par), dbd, dsc, m->strip_bnd, m->strip_win, m->wincap, m->strip_grid)
-                             : launch_sw_band_scalar_raw(m->stream, dq, dqo, dp, dro, ntask, to_par(par), dbd, dsc, drows, rowlen);
-    if (lr) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
-    else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
-    else (void)hipMemcpy(scores, dsc, (size_t)ntask * 4, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(dq); (void)hipFree(dp); (void)hipFree(dqo); (void)hipFree(dro); (void)hipFree(dsc); (void)hipFree(dbd); (void)hipFree(drows);
-  return rv;
-}
-
-static_assert(sizeof(smaltgpu_band_node) == sizeof(BandNodeOut), "smaltgpu_band_node is BandNodeOut");
-static_assert((int)SMALTGPU_BAND_NFORMS == (int)BF_NFORMS && (int)SMALTGPU_BAND_SCALAR == (int)BF_SCALAR && (int)SMALTGPU_BAND_STRIP8 == (int)BF_STRIP8, "form numbers");
-
-extern "C" int smaltgpu_band_geometry(int band_l, int band_r, int qs, int qe, int qlen, int s_left, int s_right, int wlen, int gap_init,
-                                       int gap_ext, int32_t *geo) {
-  if (!geo || qlen < 1 || wlen < 1) return fail(SMALTGPU_EARG, "bad argument");
-  Band b;
-  if (band_init(b, band_l, band_r, qs, qe, qlen, s_left, s_right, wlen)) return 1;
-  const int32_t v[14] = {b.band_width, b.l_edge_orig, b.r_edge_orig, b.l_edge, b.r_edge, b.s_left_orig, b.s_left, b.s_len, b.s_totlen,
-                         b.q_left_orig, b.q_left, b.q_len, b.q_totlen, band_form_production(b, -gap_init, -gap_ext)};
-  memcpy(geo, v, sizeof(v));
-  return 0;
-}
-
-extern "C" int smaltgpu_band_align_nodes(smaltgpu_mapper *m, const uint8_t *qcodes, const uint32_t *q_off, const uint8_t *rcodes,
-                                          const uint32_t *r_off, uint32_t ntask, const smaltgpu_params *par, const int32_t *band, const int32_t *iv,
-                                          int minscore, int form, int lds, int tw, smaltgpu_band_node *out, uint8_t *dstr) {
-  if (!m || !qcodes || !q_off || !rcodes || !r_off || !par || !band || !iv || !out || !dstr) return fail(SMALTGPU_EARG, "null argument");
-  if (form < 0 || form >= (int)BF_NFORMS || (lds && form != (int)BF_ROWS)) return fail(SMALTGPU_EARG, "unknown form");
-  const MapPar p = to_par(par);
-  const int gi = -p.gap_init, ge = -p.gap_ext;
-  if (form == (int)BF_ROWS && !(gi >= ge && ge >= 0)) return fail(SMALTGPU_EARG, "the row form needs gap_init >= gap_ext >= 0");
-  // per task: the form's precondition on the band the kernel will set up, and the room its directions take
-  std::vector<uint64_t> dir_off((size_t)ntask + 1, 0);
-  std::vector<uint32_t> dstr_off((size_t)ntask + 1, 0);
-  uint32_t qmaxlen = 0, rmaxlen = 0;
-  for (uint32_t t = 0; t < ntask; t++) {
-    if (q_off[t + 1] <= q_off[t] || r_off[t + 1] <= r_off[t]) return fail(SMALTGPU_EARG, "empty read or window");
-    const uint32_t ql = q_off[t + 1] - q_off[t], wl = r_off[t + 1] - r_off[t];
-    if (ql > (1u << 20) || wl > (1u << 20)) return fail(SMALTGPU_EARG, "task too long");
-    if (lds && (ql > NODE_LDS_CODES || wl > NODE_LDS_CODES)) return fail(SMALTGPU_EARG, "read or window too long for the LDS stage");
-    if (ql > qmaxlen) qmaxlen = ql;
-    if (wl > rmaxlen) rmaxlen = wl;
-    Band b;
-    uint64_t need = 16;
-    if (!band_init(b, band[4 * t], band[4 * t + 1], band[4 * t + 2], band[4 * t + 3], (int)ql, iv[2 * t], iv[2 * t + 1], (int)wl) &&
-        b.s_left < b.s_len && b.band_width >= 0) {
-      if (!band_form_ok(form, b, gi, ge)) return fail(SMALTGPU_EARG, "a task's band is outside the form's precondition");
-      need = band_dir_bytes(form, b, tw != 0) + 2 * (uint64_t)wl + 256;
-    }
-    dir_off[t + 1] = dir_off[t] + ((need + 15) & ~(uint64_t)15);
-    dstr_off[t + 1] = dstr_off[t] + ql + wl + 16;
-  }
-  if (dir_off[ntask] > (4ull << 30)) return fail(SMALTGPU_EARG, "direction matrices above 4 GiB");
-  std::vector<uint8_t> wdec(r_off[ntask] + 1);                       // window codes as the mapper decodes them (ref_code)
-  for (size_t o = 0; o < r_off[ntask]; o++) { const uint8_t c = rcodes[o] & 7; wdec[o] = c == 7 ? 0 : ((c == 6 || c == 4) ? 5 : c); }
-  HIPCHK(hipSetDevice(m->device));
-  const bool strip = form == (int)BF_STRIP8 || form == (int)BF_STRIP16;
-  const uint32_t rowlen = qmaxlen + rmaxlen + 2;
-  const size_t nbnd = strip ? (size_t)ntask * 2 * rmaxlen : 1, nrows = form == (int)BF_SCALAR ? (size_t)ntask * 2 * rowlen : 1;
-  uint8_t *dq = nullptr, *dw = nullptr, *ddir = nullptr, *dtmp = nullptr, *dds = nullptr;
-  uint32_t *dqo = nullptr, *dro = nullptr, *ddso = nullptr; uint64_t *ddo = nullptr; int32_t *dbd = nullptr, *div = nullptr;
-  int2 *dbnd = nullptr; int *drows = nullptr; BandNodeOut *dout = nullptr;
-  int rv = 0;
-  if (dalloc(&dq, q_off[ntask] + 16) || dalloc(&dw, r_off[ntask] + 16) || dalloc(&ddir, dir_off[ntask] + 16) || dalloc(&dtmp, (size_t)dstr_off[ntask] + 16) ||
-      dalloc(&dds, (size_t)dstr_off[ntask] + 16) || dalloc(&dqo, (size_t)ntask + 1) || dalloc(&dro, (size_t)ntask + 1) || dalloc(&ddso, (size_t)ntask + 1) ||
-      dalloc(&ddo, (size_t)ntask + 1) || dalloc(&dbd, 4 * (size_t)ntask + 4) || dalloc(&div, 2 * (size_t)ntask + 2) || dalloc(&dbnd, nbnd) ||
-      dalloc(&drows, nrows) || dalloc(&dout, (size_t)ntask + 1)) rv = SMALTGPU_ENOMEM;
-  if (!rv) {
-    (void)hipMemcpy(dq, qcodes, q_off[ntask], hipMemcpyHostToDevice);
-    (void)hipMemcpy(dw, wdec.data(), r_off[ntask], hipMemcpyHostToDevice);
-    (void)hipMemcpy(dqo, q_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dro, r_off, ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(ddso, dstr_off.data(), ((size_t)ntask + 1) * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(ddo, dir_off.data(), ((size_t)ntask + 1) * 8, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dbd, band, (size_t)ntask * 16, hipMemcpyHostToDevice);
-    (void)hipMemcpy(div, iv, (size_t)ntask * 8, hipMemcpyHostToDevice);
-    (void)hipMemset(ddir, 0, dir_off[ntask] + 16);
-    (void)hipMemset(dds, 0, (size_t)dstr_off[ntask] + 16);
-    (void)hipMemset(drows, 0, nrows * sizeof(int));
-    (void)hipMemset(dbnd, 0, nbnd * sizeof(int2));
-    BandNodeArgs a;
-    a.q = dq; a.q_off = dqo; a.win = dw; a.r_off = dro; a.ntask = ntask; a.band = dbd; a.iv = div;
-    a.minscore = minscore; a.form = form; a.lds = lds; a.tw = tw;
-    a.dir = ddir; a.dir_off = ddo; a.bnd = dbnd; a.bndcap = rmaxlen; a.rows = drows; a.rowlen = rowlen;
-    a.dtmp = dtmp; a.dstr = dds; a.dstr_off = ddso; a.out = dout;
-    if (launch_band_nodes(m->stream, a, p)) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
-    else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
-    else {
-      (void)hipMemcpy(out, dout, (size_t)ntask * sizeof(BandNodeOut), hipMemcpyDeviceToHost);
-      (void)hipMemcpy(dstr, dds, dstr_off[ntask], hipMemcpyDeviceToHost);
-    }
-  }
-  (void)hipFree(dq); (void)hipFree(dw); (void)hipFree(ddir); (void)hipFree(dtmp); (void)hipFree(dds); (void)hipFree(dqo); (void)hipFree(dro);
-  (void)hipFree(ddso); (void)hipFree(ddo); (void)hipFree(dbd); (void)hipFree(div); (void)hipFree(dbnd); (void)hipFree(drows); (void)hipFree(dout);
-  return rv;
-}
-
-extern "C" int smaltgpu_sw_rowframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
-  return sw16_rowframe_max_steps(match, mismatch, gap_init, gap_ext, ncols);
-}
-
-extern "C" int smaltgpu_sw_pairframe_max_steps(int match, int mismatch, int gap_init, int gap_ext, int ncols) {
-  return sw16_pairframe_max_steps(match, mismatch, gap_init, gap_ext, ncols);
-}
-
-extern "C" int smaltgpu_rank_sort_batch(smaltgpu_mapper *m, const uint32_t *keys, const uint32_t *off, uint32_t narr, int nneed, int in_lds,
-                                         int instance, uint32_t *out_keys, uint32_t *out_idx) {
-  if (!m || !keys || !off || !out_keys || !out_idx) return fail(SMALTGPU_EARG, "null argument");
-  if (instance != 0 && instance != 1) return fail(SMALTGPU_EARG, "unknown instance %d", instance);
-  HIPCHK(hipSetDevice(m->device));
-  const size_t tot = off[narr];
-  const uint32_t nlim = instance ? (1u << SEED_IDXBITS) - 1u : (1u << 22), klim = instance ? 1u << (32 - SEED_IDXBITS) : 1024u;
-  for (uint32_t t = 0; t < narr; t++) if (off[t + 1] < off[t] || off[t + 1] - off[t] > nlim) return fail(SMALTGPU_EARG, "bad array offsets");
-  for (size_t i = 0; i < tot; i++) if (keys[i] >= klim) return fail(SMALTGPU_EARG, "key out of range");
-  uint32_t *dk = nullptr, *doff = nullptr, *dkv = nullptr, *dok = nullptr, *doi = nullptr;
-  int rv = 0;
-  if (dalloc(&dk, tot + 1) || dalloc(&doff, (size_t)narr + 1) || dalloc(&dkv, tot + 1) || dalloc(&dok, tot + 1) || dalloc(&doi, tot + 1)) rv = SMALTGPU_ENOMEM;
-  if (!rv) {
-    (void)hipMemcpy(dk, keys, tot * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(doff, off, ((size_t)narr + 1) * 4, hipMemcpyHostToDevice);
-    if (instance) launch_seed_sort_raw(m->stream, dk, doff, narr, dok, doi);
-    else launch_rank_sort_raw(m->stream, dk, doff, narr, nneed, in_lds, dkv, dok, doi);
-    if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
-    else { (void)hipMemcpy(out_keys, dok, tot * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(out_idx, doi, tot * 4, hipMemcpyDeviceToHost); }
-  }
-  (void)hipFree(dk); (void)hipFree(doff); (void)hipFree(dkv); (void)hipFree(dok); (void)hipFree(doi);
-  return rv;
-}
-
-// S3 on its own: the launches of run_pipeline up to and including k_hits, on the mapper's buffers, and host copies of what they left
-extern "C" int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
-                                   const smaltgpu_params *par, uint32_t window, uint64_t pool_keys, smaltgpu_hits_out *out) {
-  static_assert(sizeof(SeedRec) == sizeof(smaltgpu_hit_seed) && sizeof(HitRun) == sizeof(smaltgpu_hit_run), "hit record layout");
-  static_assert((uint32_t)HITRUN_NONE == (uint32_t)SMALTGPU_HITRUN_NONE && (uint32_t)HITRUN_SORTED == (uint32_t)SMALTGPU_HITRUN_SORTED &&
-                (uint32_t)HITRUN_OVERFLOW == (uint32_t)SMALTGPU_HITRUN_OVERFLOW, "hit run modes");
-  if (!m || !bases || !read_off || !par || !out) return fail(SMALTGPU_EARG, "null argument");
-  if (!m->hits_W || !m->b_hitrun) return fail(SMALTGPU_EARG, "this mapper keeps S3 inside the candidate stage (max_read_len > 248 or SMALTGPU_HITS_SPLIT=0)");
-  if (nreads > m->max_reads || read_off[nreads] - read_off[0] > m->max_bases) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity");
-  if (pool_keys > m->b.hitpool_cap) return fail(SMALTGPU_EARG, "pool_keys exceeds the pool's allocation (%llu keys)", (unsigned long long)m->b.hitpool_cap);
-  int rv = check_par(m, par);
-  if (rv) return rv;
-  uint32_t W = window ? window : m->hits_W;
-  if (W < 256) W = 256;
-  if (W > 1024) W = 1024;
-  const uint64_t cap = pool_keys ? pool_keys : m->b.hitpool_cap;
-  const uint64_t total = read_off[nreads] - read_off[0];
-  m->h_off.resize((size_t)nreads + 1);
-  for (uint32_t i = 0; i <= nreads; i++) {
-    m->h_off[i] = read_off[i] - read_off[0];
-    if (i && m->h_off[i] - m->h_off[i - 1] > m->max_len) return fail(SMALTGPU_EARG, "read %u is longer than the mapper's max_read_len", i - 1);
-  }
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  if (total) HIPCHK(hipMemcpyAsync(m->d_bases, bases + read_off[0], total, hipMemcpyHostToDevice, s));
-  if (quals && total) HIPCHK(hipMemcpyAsync(m->d_quals, quals + read_off[0], total, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(m->d_off, m->h_off.data(), ((size_t)nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-  // the batch as run_pipeline sets it up for a plain call
-  Batch &b = m->b;
-  const DevIndex &d = m->ix->d;
-  const MapPar p = to_par(par);
-  b.iv_off = nullptr; b.iv = nullptr; b.min_sw = nullptr; b.prevmax = nullptr; b.fine_idx = nullptr; b.fine_pos = nullptr; b.fine_off = nullptr;
-  b.alloc_len = nullptr; b.seed_range = nullptr; b.totals_only = 0; b.raw_results = 0;
-  m->last_fine = false; m->last_par = p; m->last_n = nreads; m->have_host_off = true; m->fetch_open = false;
-  b.nreads = nreads; b.codes = m->d_codes; b.codes_rc = m->d_codes_rc; b.qual = quals ? m->d_quals : nullptr; b.read_off = m->d_off;
-  b.hitrun = m->b_hitrun;
-  Batch hb = b;
-  hb.hitpool_cap = cap;                                   // this call only
-  HIPCHK(hipMemsetAsync(m->d_counters, 0, smaltgpu_mapper::CT_BYTES, s));
-  rv = launch_encode(s, m->d_bases, m->d_off, nreads, m->d_codes, m->d_codes_rc);
-  if (!rv) rv = launch_seed(s, hb, d, p, m->seed_scr, m->seed_bytes, m->seed_slots);
-  if (!rv) rv = launch_hits(s, hb, d, p, W, m->cg.tab, m->hits_wg);
-  if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
-  HIPCHK(hipStreamSynchronize(s));
-  smaltgpu_mapper::HitsHost &h = m->hh;
-  const size_t ns = 2 * (size_t)nreads, stride = m->qmax;
-  h.hi.resize(ns ? ns : 1); h.n_seeds.assign(ns ? ns : 1, 0); h.seed_rank.assign(ns ? ns : 1, 0); h.status.assign(ns ? ns : 1, 0);
-  h.seeds.resize(ns * stride + 1); h.qmask.resize(ns * stride + 1); h.runs.resize(ns ? ns : 1);
-  unsigned long long count = 0;
-  if (ns) {
-    HIPCHK(hipMemcpy(h.hi.data(), b.hi, ns * sizeof(HitInfoHdr), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.seeds.data(), b.seeds, ns * stride * sizeof(SeedRec), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.qmask.data(), b.qmask, ns * stride, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.runs.data(), m->b_hitrun, ns * sizeof(HitRun), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&count, b.hit_count, sizeof(count), hipMemcpyDeviceToHost));
-  }
-  for (size_t i = 0; i < ns; i++) { h.n_seeds[i] = h.hi[i].n_seeds; h.seed_rank[i] = h.hi[i].seed_rank; h.status[i] = h.hi[i].status; }
-  const uint64_t npool = count < cap ? count : cap;
-  h.pool.resize(npool ? npool : 1);
-  if (npool) HIPCHK(hipMemcpy(h.pool.data(), b.hitpool, npool * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  memset(out, 0, sizeof(*out));
-  out->nstrands = (uint32_t)ns; out->stride = (uint32_t)stride; out->window = W; out->tab = m->cg.tab;
-  out->n_seeds = h.n_seeds.data(); out->seed_rank = h.seed_rank.data(); out->status = h.status.data();
-  out->seeds = (const smaltgpu_hit_seed *)h.seeds.data(); out->qmask = h.qmask.data(); out->runs = (const smaltgpu_hit_run *)h.runs.data();
-  out->hit_count = count; out->pool_cap = cap; out->pool = h.pool.data();
-  return SMALTGPU_OK;
-}
-
-// k_fine_index on its own: the context of a fine round goes up as for a mapping call (upload_ctx), the position buffer and the
-// index rows are filled with a guard pattern, launch_fine_index runs on the mapper's buffers, and everything comes back
-extern "C" int smaltgpu_fine_index_batch(smaltgpu_mapper *m, uint32_t nreads, const uint64_t *iv_off, const smaltgpu_interval *iv, uint32_t grid,
-                                         uint32_t guard, smaltgpu_fine_out *out) {
-  if (!m || !iv_off || !out) return fail(SMALTGPU_EARG, "null argument");
-  if (nreads > m->max_reads) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity");
-  HIPCHK(hipSetDevice(m->device));
-  smaltgpu_callctx ctx;
-  memset(&ctx, 0, sizeof(ctx));
-  ctx.iv_off = iv_off; ctx.iv = iv; ctx.fine_index = 1;
-  CtxDev cd;
-  int rv = upload_ctx(m, &ctx, nreads, &cd);
-  if (rv) return rv;
-  hipStream_t s = m->stream;
-  const size_t npos = (size_t)m->h_fineoff[nreads] + 1, nidx = (size_t)nreads * FINE_IDX_STRIDE;      // (one word behind the last slice)
-  std::vector<uint32_t> &hp = m->h_finepos, &hi = m->h_fineidx;
-  hp.assign(npos, guard); hi.assign(nidx ? nidx : 1, guard);
-  HIPCHK(hipMemcpyAsync(cd.fine_pos, hp.data(), npos * 4, hipMemcpyHostToDevice, s));
-  if (nidx) HIPCHK(hipMemcpyAsync(cd.fine_idx, hi.data(), nidx * 4, hipMemcpyHostToDevice, s));
-  Batch b = m->b;
-  b.nreads = nreads; b.iv_off = cd.iv_off; b.iv = cd.iv; b.fine_idx = cd.fine_idx; b.fine_pos = cd.fine_pos; b.fine_off = cd.fine_off;
-  rv = launch_fine_index(s, b, m->ix->d, grid);
-  if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipMemcpy(hp.data(), cd.fine_pos, npos * 4, hipMemcpyDeviceToHost));
-  if (nidx) HIPCHK(hipMemcpy(hi.data(), cd.fine_idx, nidx * 4, hipMemcpyDeviceToHost));
-  out->nreads = nreads; out->idx_stride = FINE_IDX_STRIDE; out->nkeys = FINE_NKEYS; out->npos = (uint64_t)npos;
-  out->fine_off = m->h_fineoff.data(); out->idx = hi.data(); out->pos = hp.data();
-  return SMALTGPU_OK;
-}
-
-extern "C" int smaltgpu_cands_geometry(smaltgpu_mapper *m, uint32_t out[8]) {
-  if (!m || !out) return fail(SMALTGPU_EARG, "null argument");
-  const bool two = m->cand_scr2 != nullptr;
-  out[0] = m->cg.hcap_strand; out[1] = m->cg.candcap; out[2] = cands_lds_bytes(m->cg);
-  out[3] = two ? m->cg2.hcap_strand : 0u; out[4] = two ? m->cg2.candcap : 0u; out[5] = two ? cands_lds_bytes(m->cg2) : 0u;
-  out[6] = m->qmax; out[7] = (uint32_t)IV_MAX;
-  return SMALTGPU_OK;
-}
-
-extern "C" int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out) {
-  if (!m || !keys || !off || !out) return fail(SMALTGPU_EARG, "null argument");
-  if (form < 0 || form > 5) return fail(SMALTGPU_EARG, "unknown form %d", form);
-  const uint32_t nmax = form == 0 ? 256u : (form == 1 ? 512u : (form <= 3 ? 1024u : 65536u));
-  for (uint32_t t = 0; t < narr; t++) if (off[t + 1] < off[t] || off[t + 1] - off[t] > nmax) return fail(SMALTGPU_EARG, "array %u does not fit form %d (at most %u keys)", t, form, nmax);
-  HIPCHK(hipSetDevice(m->device));
-  const size_t tot = narr ? off[narr] : 0;
-  uint64_t *dk = nullptr, *dout = nullptr;
-  uint32_t *doff = nullptr;
-  int rv = 0;
-  if (dalloc(&dk, tot + 1) || dalloc(&dout, tot + 1) || dalloc(&doff, (size_t)narr + 1)) rv = SMALTGPU_ENOMEM;
-  if (!rv) {
-    if (tot) (void)hipMemcpy(dk, keys, tot * 8, hipMemcpyHostToDevice);
-    (void)hipMemcpy(doff, off, ((size_t)narr + 1) * 4, hipMemcpyHostToDevice);
-    if (form >= 4 ? launch_sort_u64_hbm_raw(m->stream, dk, doff, narr, form, dout) : launch_sort_u64_raw(m->stream, dk, doff, narr, form, dout)) rv = fail(SMALTGPU_ENODEV, "kernel launch failed");
-    else if (hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
-    else if (tot) (void)hipMemcpy(out, dout, tot * 8, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(dk); (void)hipFree(dout); (void)hipFree(doff);
-  return rv;
-}
-
-// S1 + S2 on their own: launch_encode and launch_seed on the mapper's buffers and nothing behind them.  The rows of the batch in
-// hi, seeds and qmask and one row behind the last strand are filled with `guard` first, so that a test sees every byte the kernel wrote.
-extern "C" int smaltgpu_seed_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
-                                   const smaltgpu_params *par, const uint32_t *seed_range, int totals_only, int scratch_home, uint32_t grid,
-                                   uint8_t guard, smaltgpu_seed_out *out) {
-  static_assert(sizeof(HitInfoHdr) == 8 * sizeof(uint32_t) && sizeof(SeedRec) == 3 * sizeof(uint32_t), "seed record layout");
-  if (!m || !bases || !read_off || !par || !out || !out->codes || !out->codes_rc || !out->hi || !out->seeds || !out->qmask) return fail(SMALTGPU_EARG, "null argument");
-  if (seed_range && totals_only) return fail(SMALTGPU_EARG, "seed_range and totals_only exclude each other (rmap.c:1076 counts the hits of whole reads)");
-  if (scratch_home != 0 && scratch_home != 1) return fail(SMALTGPU_EARG, "scratch_home is 0 or 1");
-  if (nreads >= m->max_reads || read_off[nreads] - read_off[0] > m->max_bases) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity (one guard row is kept behind the last strand)");
-  int rv = check_par(m, par);
-  if (rv) return rv;
-  const bool hbm = scratch_home == 1 || m->seed_bytes > 48 * 1024;
-  if (hbm && grid > m->seed_slots) return fail(SMALTGPU_EARG, "grid %u exceeds the %u scratch slots", grid, m->seed_slots);
-  const uint64_t total = read_off[nreads] - read_off[0];
-  m->h_off.resize((size_t)nreads + 1);
-  for (uint32_t i = 0; i <= nreads; i++) {
-    m->h_off[i] = read_off[i] - read_off[0];
-    if (i && m->h_off[i] - m->h_off[i - 1] > m->max_len) return fail(SMALTGPU_EARG, "read %u is longer than the mapper's max_read_len", i - 1);
-  }
-  HIPCHK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  if (total) HIPCHK(hipMemcpyAsync(m->d_bases, bases + read_off[0], total, hipMemcpyHostToDevice, s));
-  if (quals && total) HIPCHK(hipMemcpyAsync(m->d_quals, quals + read_off[0], total, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(m->d_off, m->h_off.data(), ((size_t)nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-  if (seed_range) {
-    if (m->cx_seedrange.ensure((size_t)(nreads ? nreads : 1) * 8)) return fail(SMALTGPU_ENOMEM, "device memory");
-    if (nreads) HIPCHK(hipMemcpyAsync(m->cx_seedrange.p, seed_range, (size_t)nreads * 8, hipMemcpyHostToDevice, s));
-  }
-  Batch &b = m->b;
-  const DevIndex &d = m->ix->d;
-  const MapPar p = to_par(par);
-  b.iv_off = nullptr; b.iv = nullptr; b.min_sw = nullptr; b.prevmax = nullptr; b.fine_idx = nullptr; b.fine_pos = nullptr; b.fine_off = nullptr;
-  b.alloc_len = nullptr; b.seed_range = seed_range ? (const uint32_t *)m->cx_seedrange.p : nullptr; b.totals_only = totals_only ? 1u : 0u; b.raw_results = 0;
-  b.hitrun = nullptr;
-  m->last_fine = false; m->last_par = p; m->last_n = nreads; m->have_host_off = true; m->fetch_open = false;
-  b.nreads = nreads; b.codes = m->d_codes; b.codes_rc = m->d_codes_rc; b.qual = quals ? m->d_quals : nullptr; b.read_off = m->d_off;
-  const size_t rows = 2 * (size_t)nreads + 1, stride = m->qmax;
-  HIPCHK(hipMemsetAsync(m->d_counters, 0, smaltgpu_mapper::CT_BYTES, s));
-  HIPCHK(hipMemsetAsync(b.hi, guard, rows * sizeof(HitInfoHdr), s));
-  HIPCHK(hipMemsetAsync(b.seeds, guard, rows * stride * sizeof(SeedRec), s));
-  HIPCHK(hipMemsetAsync(b.qmask, guard, rows * stride, s));
-  // scratch: the mapper's own, or HBM slots for this call only where the mapper's fits LDS
-  uint8_t *scr = m->seed_scr, *own = nullptr;
-  const uint32_t items = 2 * nreads;
-  const uint32_t g = grid ? grid : (hbm ? (items < m->seed_slots ? items : m->seed_slots) : (items < 32768u ? items : 32768u));
-  if (scratch_home == 1 && !scr && g) {
-    HIPCHK(hipMalloc((void **)&own, m->seed_bytes * (size_t)g));
-    scr = own;
-  }
-  rv = launch_encode(s, m->d_bases, m->d_off, nreads, m->d_codes, m->d_codes_rc);
-  if (!rv) rv = launch_seed(s, b, d, p, scr, m->seed_bytes, own ? g : m->seed_slots, scratch_home == 1, grid);
-  b.seed_range = nullptr; b.totals_only = 0;
-  hipError_t he = hipStreamSynchronize(s);
-  if (own) (void)hipFree(own);
-  if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
-  HIPCHK(he);
-  unsigned long long work[WK_NWORK];
-  if (total) { HIPCHK(hipMemcpy(out->codes, m->d_codes, total, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out->codes_rc, m->d_codes_rc, total, hipMemcpyDeviceToHost)); }
-  HIPCHK(hipMemcpy(out->hi, b.hi, rows * sizeof(HitInfoHdr), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(out->seeds, b.seeds, rows * stride * sizeof(SeedRec), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(out->qmask, b.qmask, rows * stride, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(work, b.work, sizeof(work), hipMemcpyDeviceToHost));
-  out->nrows = (uint32_t)rows; out->stride = (uint32_t)stride; out->in_lds = hbm ? 0u : 1u; out->grid = nreads ? g : 0u; out->lookups = work[WK_LOOKUPS];
-  return SMALTGPU_OK;
-}
-
-// k_gather_reads on its own: the two host batches become the two resident batches, the mapper's read buffers are filled with
-// `guard`, launch_gather_reads runs with `ids`, and the gathered bytes come back with the `tail` bytes behind the last read
-extern "C" int smaltgpu_gather_batch(smaltgpu_mapper *m, const uint8_t *const bases[2], const uint8_t *const quals[2], const uint64_t *const read_off[2],
-                                     const uint32_t nreads[2], const uint32_t *ids, uint32_t nids, uint8_t guard, uint32_t tail,
-                                     uint8_t *dst_bases, uint8_t *dst_quals, uint64_t *dst_off) {
-  if (!m || !bases || !read_off || !nreads || !ids || !dst_bases || !dst_off || !bases[0] || !bases[1] || !read_off[0] || !read_off[1]) return fail(SMALTGPU_EARG, "null argument");
-  if (quals && (!quals[0] != !quals[1])) return fail(SMALTGPU_EARG, "qualities: both batches or neither");
-  const bool wq_in = quals && quals[0];
-  if (wq_in && !dst_quals) return fail(SMALTGPU_EARG, "null argument");
-  if (nids > m->max_reads || tail > 16) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity");
-  for (int w = 0; w < 2; w++) if (read_off[w][0] != 0) return fail(SMALTGPU_EARG, "offsets start at 0");
-  HIPCHK(hipSetDevice(m->device));
-  uint8_t *db[2] = {nullptr, nullptr}, *dq[2] = {nullptr, nullptr};
-  uint64_t *dof[2] = {nullptr, nullptr};
-  int rv = 0;
-  for (int w = 0; w < 2 && !rv; w++) {
-    const size_t tot = read_off[w][nreads[w]];
-    if (dalloc(&db[w], tot + 16) || dalloc(&dof[w], (size_t)nreads[w] + 1) || (wq_in && dalloc(&dq[w], tot + 16))) { rv = SMALTGPU_ENOMEM; break; }
-    if (tot) (void)hipMemcpy(db[w], bases[w], tot, hipMemcpyHostToDevice);
-    if (tot && wq_in) (void)hipMemcpy(dq[w], quals[w], tot, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dof[w], read_off[w], ((size_t)nreads[w] + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-  }
-  if (!rv) {
-    smaltgpu_resident_reads src;
-    memset(&src, 0, sizeof(src));
-    for (int w = 0; w < 2; w++) { src.d_bases[w] = db[w]; src.d_quals[w] = dq[w]; src.d_read_off[w] = dof[w]; src.read_off[w] = read_off[w]; src.nreads[w] = nreads[w]; }
-    bool wq = false;
-    if (hipMemsetAsync(m->d_bases, guard, m->max_bases + 16, m->stream) != hipSuccess || hipMemsetAsync(m->d_quals, guard, m->max_bases + 16, m->stream) != hipSuccess)
-      rv = fail(SMALTGPU_ENODEV, "memset failed");
-    if (!rv) rv = gather_round(m, &src, ids, nids, &wq);
-    if (!rv && hipStreamSynchronize(m->stream) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "kernel failed");
-    if (!rv) {
-      const size_t tot = m->h_off[nids];
-      (void)hipMemcpy(dst_bases, m->d_bases, tot + tail, hipMemcpyDeviceToHost);
-      if (dst_quals) (void)hipMemcpy(dst_quals, m->d_quals, tot + tail, hipMemcpyDeviceToHost);      // (without qualities: the guard, untouched)
-      memcpy(dst_off, m->h_off.data(), ((size_t)nids + 1) * sizeof(uint64_t));
-    }
-  }
-  for (int w = 0; w < 2; w++) { (void)hipFree(db[w]); (void)hipFree(dq[w]); (void)hipFree(dof[w]); }
-  return rv;
 }
