@@ -711,6 +711,45 @@ int smaltgpu_cands_geometry(smaltgpu_mapper *m, uint32_t out[8]);
  * place in out and sorted there, at most 65536 keys.  SMALTGPU_EARG for a longer array. */
 int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out);
 
+/* O1 and the K3 driver on their own (kernels k_replay and k_align): the reads are uploaded and encoded, the caller's ranked
+ * candidates WITH their first-pass scores take the place of what the candidate stage and the score kernels leave in the batch,
+ * and the tail of a mapping call runs on the mapper's own scratch, slots and capacities: k_replay, then both passes of k_align.
+ * The production score kernels are not part of it (their task routing follows lists the candidate stage builds), nor are the
+ * complexity-weighted scores (SMALTGPU_EARG with SMALTGPU_FLG_CMPLXW).  Read r owns cands[cand_off[r] .. cand_off[r + 1]) in rank
+ * order and cover_deficit[2 r + strand].  Of ctx (may be NULL) prev_max, min_swatscor and raw_alignments are honoured;
+ * SMALTGPU_EARG if iv_off, fine_index or seed_range is set.  flags: SMALTGPU_ALIGN_CANDS_ANTIDIAG or 0.
+ * Nothing is repaired: SMALTGPU_EARG unless the offsets ascend, the candidates fit the mapper's candidate pool, and every
+ * candidate has -1 <= sqidx < nseq (-1: the window lies in the concatenated set), rs <= re inside that sequence and
+ * 0 <= swscor <= read length x match (a larger score is the reference's error and cannot come from the score kernels).
+ * The results come back as from a mapping call (out->batch; the return value is the first per-read error, as there), with the
+ * hit numbers of the stats 0; out->ctl[r] is what k_replay left for read r; out->n_deferred counts the reads the first pass
+ * of k_align handed to the second.  The arrays belong to the mapper and hold until its next call. */
+enum { SMALTGPU_CAND_REVERSE = 1, SMALTGPU_CAND_ERR = 2 /* the candidate stage marked the candidate as broken (RCF_ERR) */ };
+enum { SMALTGPU_ALIGN_CANDS_ANTIDIAG = 0x100 /* narrow bands in the anti-diagonal form, as under SMALTGPU_ALIGN_ANTIDIAG */ };
+typedef struct smaltgpu_cand {
+  uint64_t rs, re;                   /* window in sequence sqidx, 0-based inclusive */
+  uint32_t qs, qe;
+  int32_t band_l, band_r;
+  int32_t sqidx;
+  uint32_t flags;                    /* SMALTGPU_CAND_* */
+  uint32_t cover;
+  int32_t swscor;                    /* first-pass score */
+} smaltgpu_cand;
+typedef struct smaltgpu_readctl {    /* scalars of mapSingleRead (rmap.c:1373-1400) as k_replay leaves them */
+  int32_t max1, max2, n_scored;
+  int32_t bandwidth_min, min_swatscor, scorlen_min;
+  int32_t go;                        /* 1: the traceback pass runs */
+  int32_t pad;
+} smaltgpu_readctl;
+typedef struct smaltgpu_align_cands_out {
+  smaltgpu_batch_out batch;
+  const smaltgpu_readctl *ctl;       /* [nreads] */
+  uint32_t n_deferred;
+} smaltgpu_align_cands_out;
+int smaltgpu_align_cands_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
+                               const smaltgpu_params *par, const smaltgpu_callctx *ctx, const uint64_t *cand_off, const smaltgpu_cand *cands,
+                               const uint32_t *cover_deficit, uint32_t flags, smaltgpu_align_cands_out *out);
+
 const char *smaltgpu_last_error(void);
 int smaltgpu_device_count(void);
 

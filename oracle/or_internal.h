@@ -45,6 +45,7 @@ struct OrMap {
   int swmax, sw2nd;
   int nseg, nseg_tot, nhit, nhit_tot, max1, max2;
   int th_bandwidth_min, th_min_swatscor, th_scorlen_min;
+  int th_go;                 /* 1: the threshold block was passed and the traceback pass ran */
   int err;
   /* retained per-(strand,seq) hit lists for dumps */
   uint64_t **hl_keep; int *hl_keep_n; int hl_keep_cnt;

@@ -102,53 +102,77 @@ static const uint8_t *fetch_window(OrMap *m, const OrCand *c)
   return m->win;
 }
 
-/* scoreRMAPCAND, rmap.c:588-788 */
-static int score_cands(OrMap *m, const int8_t M[8][8], int *max1, int *max2)
+/* The body of scoreRMAPCAND's loop (rmap.c:588-788) in two steps, shared by score_cands (candidates of the segment stage) and
+ * or_map_injected (candidates of the caller). */
+
+/* first-pass score of one candidate by the K2a / K2b predicate, rmap.c:700-754 */
+static int score_one(OrMap *m, const int8_t M[8][8], OrCand *c)
+{
+  const OrParams *p = &m->par;
+  const uint32_t qlen = m->qlen;
+  const uint8_t *win, *q;
+  uint32_t wlen;
+  int simd, rv;
+  if (c->qe > INT_MAX || c->re < c->rs || c->re - c->rs > INT_MAX) return OR_ERR;
+  win = fetch_window(m, c);
+  wlen = (uint32_t) (c->re - c->rs + 1);
+  q = m->read[c->flags & 1];
+  simd = (qlen >= MINLEN_QUERY_STRIPED && ((uint32_t) (c->band_r - c->band_l)*BWSCAL_QLEN) > qlen &&
+          c->qs == 0 && c->qe >= qlen - 1);     /* rmap.c:715-718 */
+  c->used_simd = simd;
+  if (simd) {
+    c->swscor = or_sw_full(q, qlen, win, wlen, M, p->gap_init, p->gap_ext);
+    if (c->swscor >= 65535) simd = 0;           /* ERRCODE_SWATEXCEED -> banded pass, :730 */
+  }
+  if (!simd) {
+    if ((rv = or_sw_band_fast(&c->swscor, q, qlen, win, (int) wlen, M, p->gap_init, p->gap_ext,
+                              c->band_l, c->band_r, (int) c->qs, (int) c->qe, 0, (int) wlen - 1))) return rv;
+  }
+  c->flags |= 2;
+  return OR_OK;
+}
+
+/* the sequential control over the scores, rmap.c:756-785: running maxima and the cover cut */
+typedef struct ScoreCtl { uint32_t max_cover, min_cover; int max1, max2; } ScoreCtl;
+
+static int score_control(const OrMap *m, const OrCand *c, ScoreCtl *sc)      /* 1: the loop ends in front of this candidate */
 {
   const OrParams *p = &m->par;
   const int mmscordiff = p->match - p->mismatch;
+  const uint32_t cover = c->cover, cdf = m->sc.cover_deficit[c->flags & 1];
+  uint32_t dcov;
+  if ((p->flags & OR_FLG_BEST) && cover + cdf < sc->min_cover) return 1;
+  if (c->swscor > sc->max2) {
+    if (c->swscor > sc->max1) {
+      sc->max2 = sc->max1; sc->max1 = c->swscor;
+      if (cover + cdf > sc->max_cover) sc->max_cover = (cover > cdf)? cover - cdf: 0;
+    } else sc->max2 = c->swscor;
+    dcov = (uint32_t) (((int) ((sc->max1 - sc->max2)/mmscordiff) + 1)*m->ix->s);
+    if (dcov + cdf + sc->min_cover < sc->max_cover) sc->min_cover = sc->max_cover - dcov;
+  }
+  return 0;
+}
+
+/* scoreRMAPCAND, rmap.c:588-788 */
+static int score_cands(OrMap *m, const int8_t M[8][8], int *max1, int *max2)
+{
   const uint32_t n_candseg = m->sc.n_sort, qlen = m->qlen;
-  uint32_t i, cover, max_cover = 0, min_cover = 0, dcov, cdf;
-  int rv;
-  if (mmscordiff < 1) return OR_ERR;
+  ScoreCtl sc = {0, 0, 0, 0};
+  uint32_t i;
+  int rv = OR_OK;
+  if (m->par.match - m->par.mismatch < 1) return OR_ERR;
   if (n_candseg + 1 > m->cap_cand) { m->cap_cand = n_candseg + 512; m->cand = realloc(m->cand, m->cap_cand*sizeof(OrCand)); }
   *max1 = *max2 = 0;
   for (i = 0; i < n_candseg; i++) {
     OrCand *c = m->cand + i;
-    const uint8_t *win, *q;
-    uint32_t wlen;
-    int simd;
     memset(c, 0, sizeof(*c));
     /* makeRMAPCANDfromSegment, rmap.c:535-586 (edgelen 0 in SIMD builds) */
-    if ((rv = or_segcands_offsets(c, &m->sc, m->ix, i, 0, qlen))) return rv;
-    cover = c->cover;
-    if (c->qe > INT_MAX || c->re < c->rs || c->re - c->rs > INT_MAX) return OR_ERR;
-    win = fetch_window(m, c);
-    wlen = (uint32_t) (c->re - c->rs + 1);
-    q = m->read[c->flags & 1];
-    simd = (qlen >= MINLEN_QUERY_STRIPED && ((uint32_t) (c->band_r - c->band_l)*BWSCAL_QLEN) > qlen &&
-            c->qs == 0 && c->qe >= qlen - 1);     /* rmap.c:715-718 */
-    c->used_simd = simd;
-    if (simd) {
-      c->swscor = or_sw_full(q, qlen, win, wlen, M, p->gap_init, p->gap_ext);
-      if (c->swscor >= 65535) simd = 0;           /* ERRCODE_SWATEXCEED -> banded pass, :730 */
-    }
-    if (!simd) {
-      if ((rv = or_sw_band_fast(&c->swscor, q, qlen, win, (int) wlen, M, p->gap_init, p->gap_ext,
-                                c->band_l, c->band_r, (int) c->qs, (int) c->qe, 0, (int) wlen - 1))) return rv;
-    }
-    c->flags |= 2;
-    cdf = m->sc.cover_deficit[c->flags & 1];
-    if ((p->flags & OR_FLG_BEST) && cover + cdf < min_cover) break;
-    if (c->swscor > *max2) {
-      if (c->swscor > *max1) {
-        *max2 = *max1; *max1 = c->swscor;
-        if (cover + cdf > max_cover) max_cover = (cover > cdf)? cover - cdf: 0;
-      } else *max2 = c->swscor;
-      dcov = (uint32_t) (((int) ((*max1 - *max2)/mmscordiff) + 1)*m->ix->s);
-      if (dcov + cdf + min_cover < max_cover) min_cover = max_cover - dcov;
-    }
+    if ((rv = or_segcands_offsets(c, &m->sc, m->ix, i, 0, qlen))) break;
+    if ((rv = score_one(m, M, c))) break;
+    if (score_control(m, c, &sc)) break;
   }
+  *max1 = sc.max1; *max2 = sc.max2;
+  if (rv) return rv;
   m->ncand = i;
   return OR_OK;
 }
@@ -231,6 +255,32 @@ static int align_cands(OrMap *m, const int8_t M[8][8], int min_swatscor, int sco
   return OR_OK;
 }
 
+/* the threshold block of mapSingleRead (rmap.c:1373-1400) and the traceback pass behind it */
+static int thresholds_and_align(OrMap *m, const int8_t M[8][8], int max1, int max2)
+{
+  const OrParams *p = &m->par;
+  const int maxscor_perfect = (int) m->qlen*p->match;
+  int scorlen_min = m->ix->k + m->ix->s, bandwidth_min, min_swatscor = p->min_swatscor, below_max = p->min_swatscor_below_max;
+  if (max1 > maxscor_perfect) return OR_ERR;
+  if (max1 < 1) return OR_OK;
+
+  /* rmap.c:1379-1400 */
+  bandwidth_min = (maxscor_perfect - max1)/(-1*p->gap_ext);
+  if (below_max >= max1) below_max = max1;
+  if (min_swatscor > max2 && max2 > 0) min_swatscor = max2;
+  if (below_max >= 0) {
+    int minswc = (max2 > 0)? max2: max1;
+    if (p->flags & OR_FLG_BEST) { if (minswc > min_swatscor) min_swatscor = minswc; }
+    else if (min_swatscor + below_max < max1) {
+      min_swatscor = max1 - below_max;
+      if (min_swatscor > minswc) min_swatscor = minswc;
+    }
+  }
+  if (min_swatscor > scorlen_min*p->match && p->match > 0) scorlen_min = min_swatscor/p->match;
+  m->th_bandwidth_min = bandwidth_min; m->th_min_swatscor = min_swatscor; m->th_scorlen_min = scorlen_min; m->th_go = 1;
+  return align_cands(m, M, min_swatscor, scorlen_min, bandwidth_min);
+}
+
 /* mapSingleRead, rmap.c:1228-1433 (without the results.c post-processing, row N1) */
 static int map_single_read(OrMap *m)
 {
@@ -239,15 +289,14 @@ static int map_single_read(OrMap *m)
   const int k = ix->k, s = ix->s;
   const int mismatchdiff = p->match - p->mismatch;
   int8_t M[8][8];
-  int scorlen_min = k + s, bandwidth_min, min_swatscor = p->min_swatscor, below_max = p->min_swatscor_below_max;
-  int max1 = 0, max2 = 0, maxscor_perfect, rv;
+  const int below_max = p->min_swatscor_below_max;
+  int max1 = 0, max2 = 0, rv;
   uint32_t min_cover = p->min_cover, min_ktup, mincov_below_max, nr, ntot;
 
   /* calcMinKtup, rmap.c:240-247 */
   min_ktup = (min_cover >= (uint32_t) (k + s))? (min_cover - k)/s: 1;
   min_cover = (min_ktup - 1)*s + k;
   if (mismatchdiff < 0 || p->gap_ext >= 0 || p->mismatch >= 0) return OR_ERR;
-  maxscor_perfect = (int) m->qlen*p->match;
   if (below_max < 0) mincov_below_max = m->qlen - 1;
   else {
     mincov_below_max = ((uint32_t) (below_max/mismatchdiff))*s;
@@ -276,24 +325,7 @@ static int map_single_read(OrMap *m)
   rv = score_cands(m, M, &max1, &max2);
   m->max1 = max1; m->max2 = max2;
   if (rv) return rv;
-  if (max1 > maxscor_perfect) return OR_ERR;
-  if (max1 < 1) return OR_OK;
-
-  /* rmap.c:1379-1400 */
-  bandwidth_min = (maxscor_perfect - max1)/(-1*p->gap_ext);
-  if (below_max >= max1) below_max = max1;
-  if (min_swatscor > max2 && max2 > 0) min_swatscor = max2;
-  if (below_max >= 0) {
-    int minswc = (max2 > 0)? max2: max1;
-    if (p->flags & OR_FLG_BEST) { if (minswc > min_swatscor) min_swatscor = minswc; }
-    else if (min_swatscor + below_max < max1) {
-      min_swatscor = max1 - below_max;
-      if (min_swatscor > minswc) min_swatscor = minswc;
-    }
-  }
-  if (min_swatscor > scorlen_min*p->match && p->match > 0) scorlen_min = min_swatscor/p->match;
-  m->th_bandwidth_min = bandwidth_min; m->th_min_swatscor = min_swatscor; m->th_scorlen_min = scorlen_min;
-  return align_cands(m, M, min_swatscor, scorlen_min, bandwidth_min);
+  return thresholds_and_align(m, M, max1, max2);
 }
 
 int or_map_single_restricted(OrMap *m, const char *bases, const char *quals, uint32_t len, const OrParams *p,
@@ -323,11 +355,9 @@ uint32_t or_map_hit_total(const OrMap *m, int ktuple_maxhit)
 
 /* rmapSingle, rmap.c:1648-1742; the second call of a split read (mapSecondary, rmap.c:1435-1505) is this function again with
  * or_map_set_seed_range + or_map_set_prevmax and OR_FLG_RAWRESULTS (the caller holds the set it appends to) */
-int or_map_single(OrMap *m, const char *bases, const char *quals, uint32_t len, const OrParams *p)
+static void begin_read(OrMap *m, const char *bases, const char *quals, uint32_t len, const OrParams *p, uint32_t seed_range[2])
 {
-  const OrIndex *ix = m->ix;
   uint32_t i;
-  int rv;
   m->par = *p;
   m->niv = m->niv_next;
   /* a call that appends to a ResultSet (rmapPair) continues that set's running score maxima: alignRMAPCANDFull raises its
@@ -337,7 +367,7 @@ int or_map_single(OrMap *m, const char *bases, const char *quals, uint32_t len, 
   const uint32_t q0 = m->seed_range[0], q1 = m->seed_range[1];
   m->seed_range[0] = m->seed_range[1] = 0;
   m->nseg = m->nseg_tot = m->nhit = m->nhit_tot = m->max1 = m->max2 = 0;
-  m->th_bandwidth_min = m->th_min_swatscor = m->th_scorlen_min = 0;
+  m->th_bandwidth_min = m->th_min_swatscor = m->th_scorlen_min = m->th_go = 0;
   m->sc.ncand = 0; m->sc.n_sort = 0;
   keep_clear(m);
   if (len + 2 > m->read_cap) {
@@ -352,6 +382,16 @@ int or_map_single(OrMap *m, const char *bases, const char *quals, uint32_t len, 
   for (i = 0; i < len; i++) { uint8_t c = m->read[0][len - 1 - i]; m->read[1][i] = (uint8_t) ((c & 4)? c: 3 - c); }
   if (quals) memcpy(m->qual, quals, len);
   m->err = OR_OK;
+  seed_range[0] = q0; seed_range[1] = q1;
+}
+
+int or_map_single(OrMap *m, const char *bases, const char *quals, uint32_t len, const OrParams *p)
+{
+  const OrIndex *ix = m->ix;
+  uint32_t sr[2];
+  int rv;
+  begin_read(m, bases, quals, len, p, sr);
+  const uint32_t q0 = sr[0], q1 = sr[1];
   if (len < (uint32_t) ix->k) { m->hi[0].n_seeds = m->hi[1].n_seeds = 0; return OR_OK; }   /* ERRCODE_SHORTSEQ swallowed */
 
   if (p->flags & OR_FLG_NOSHRTINFO) {          /* initRMAPINFO, rmap.c:1027-1044 (with a stretch of the read: mapSecondary, rmap.c:1483) */
@@ -365,6 +405,46 @@ int or_map_single(OrMap *m, const char *bases, const char *quals, uint32_t len, 
   rv = map_single_read(m);
   m->err = rv;
   return rv;
+}
+
+/* The control of scoreRMAPCAND, the threshold block and the traceback pass over candidates the caller provides in rank order,
+ * in place of those of the segment stage: what follows fillRMAPBUFF in mapSingleRead.  rescore != 0: each candidate is scored
+ * first, by the predicate of the score pass; otherwise cands[i].swscor stands.  Seeding does not run: the hit numbers stay 0. */
+int or_map_injected(OrMap *m, const char *bases, uint32_t len, const OrParams *p, const OrCand *cands, uint32_t ncand,
+                    const uint32_t cover_deficit[2], int rescore)
+{
+  int8_t M[8][8];
+  ScoreCtl sc = {0, 0, 0, 0};
+  uint32_t sr[2], i;
+  int rv = OR_OK;
+  begin_read(m, bases, NULL, len, p, sr);
+  if (len < (uint32_t) m->ix->k) return OR_OK;
+  if (p->match - p->mismatch < 1 || p->gap_ext >= 0 || p->mismatch >= 0) return (m->err = OR_ERR);
+  or_score_matrix(M, p->match, p->mismatch);
+  or_segcands_blank(&m->sc);
+  m->sc.cover_deficit[0] = cover_deficit[0]; m->sc.cover_deficit[1] = cover_deficit[1];
+  m->nseg = m->nseg_tot = (int) ncand;
+  if (ncand + 1 > m->cap_cand) { m->cap_cand = ncand + 512; m->cand = realloc(m->cand, m->cap_cand*sizeof(OrCand)); }
+  for (i = 0; i < ncand; i++) {
+    OrCand *c = m->cand + i;
+    *c = cands[i];
+    c->flags &= 1;
+    if (rescore) { if ((rv = score_one(m, M, c))) break; }
+    else c->flags |= 2;
+    if (score_control(m, c, &sc)) break;
+  }
+  m->max1 = sc.max1; m->max2 = sc.max2;
+  if (!rv) {
+    m->ncand = i;
+    rv = thresholds_and_align(m, M, sc.max1, sc.max2);
+  }
+  m->err = rv;
+  return rv;
+}
+
+void or_map_thresholds(const OrMap *m, int out[4])
+{
+  out[0] = m->th_bandwidth_min; out[1] = m->th_min_swatscor; out[2] = m->th_scorlen_min; out[3] = m->th_go;
 }
 
 long or_map_dump_str(const OrMap *m, unsigned long long readno, const char *name, int with_hitlists, char *buf, size_t cap)

@@ -137,6 +137,16 @@ void or_map_set_prevmax(OrMap *m, int swmax, int sw2nd);
  * hashCollectHitInfo with a range (hashhit.c:987, :536-551), as mapSecondary (rmap.c:1435-1505) calls it for the part of a
  * split read that its best alignment leaves uncovered. */
 void or_map_set_seed_range(OrMap *m, uint32_t first, uint32_t last);
+/* mapSingleRead from the score pass on (rmap.c:1341-1433) over `ncand` candidates of the caller in rank order, in place of those
+ * of the segment stage: the sequential control of scoreRMAPCAND (running maxima, cover cut), the threshold block and the
+ * traceback pass.  Of an OrCand the fields flags (bit 0: reverse), qs, qe, rs, re, band_l, band_r, sqidx, cover and swscor are read.
+ * rescore != 0: every candidate is scored first by the K2a / K2b predicate, as scoreRMAPCAND does; else swscor is taken as given.
+ * cover_deficit: per strand.  or_map_set_prevmax and OR_FLG_RAWRESULTS apply as for or_map_single; nothing is seeded. */
+int or_map_injected(OrMap *m, const char *bases, uint32_t len, const OrParams *p, const OrCand *cands, uint32_t ncand,
+                    const uint32_t cover_deficit[2], int rescore);
+/* thresholds of the last read's threshold block (rmap.c:1373-1400): bandwidth_min, min_swatscor, scorlen_min, and whether the
+ * block was passed, i.e. the traceback pass ran (all 0 otherwise) */
+void or_map_thresholds(const OrMap *m, int out[4]);
 /* calcTotalNumberOfHits (rmap.c:1076) of the last read: what rmapPair compares to pick the mate it maps first */
 uint32_t or_map_hit_total(const OrMap *m, int ktuple_maxhit);
 /* print the stage state of the last read in the refdump line format */

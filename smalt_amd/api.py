@@ -143,6 +143,22 @@ class SeedOut(C.Structure):            # smaltgpu_seed_out
                 ("nrows", C.c_uint32), ("stride", C.c_uint32), ("in_lds", C.c_uint32), ("grid", C.c_uint32), ("lookups", C.c_uint64)]
 
 
+class Cand(C.Structure):               # smaltgpu_cand
+    _fields_ = [("rs", C.c_uint64), ("re", C.c_uint64), ("qs", C.c_uint32), ("qe", C.c_uint32), ("band_l", C.c_int32), ("band_r", C.c_int32),
+                ("sqidx", C.c_int32), ("flags", C.c_uint32), ("cover", C.c_uint32), ("swscor", C.c_int32)]
+
+
+class ReadCtl(C.Structure):            # smaltgpu_readctl
+    _fields_ = [("max1", C.c_int32), ("max2", C.c_int32), ("n_scored", C.c_int32), ("bandwidth_min", C.c_int32), ("min_swatscor", C.c_int32),
+                ("scorlen_min", C.c_int32), ("go", C.c_int32), ("pad", C.c_int32)]
+
+
+class AlignCandsOut(C.Structure):      # smaltgpu_align_cands_out
+    _fields_ = [("batch", BatchOut), ("ctl", C.POINTER(ReadCtl)), ("n_deferred", C.c_uint32)]
+
+
+CAND_REVERSE, CAND_ERR = 1, 2                                  # SMALTGPU_CAND_*
+ALIGN_CANDS_ANTIDIAG = 0x100                                   # SMALTGPU_ALIGN_CANDS_ANTIDIAG
 HITRUN_NONE, HITRUN_SORTED, HITRUN_OVERFLOW = 0, 1, 2         # SMALTGPU_HITRUN_*
 SORT_REG4, SORT_REG8, SORT_REG16, SORT_LDS, SORT_HBM, SORT_CHUNKED = 0, 1, 2, 3, 4, 5        # forms of smaltgpu_sort_u64_batch
 
@@ -263,6 +279,8 @@ def lib():
                                             C.c_uint32, C.c_uint8, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.smaltgpu_hits_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.c_uint32, C.c_uint64,
                                           C.POINTER(HitsOut)]
+        L.smaltgpu_align_cands_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.POINTER(CallCtx),
+                                                 C.POINTER(C.c_uint64), C.POINTER(Cand), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AlignCandsOut)]
         L.smaltgpu_fine_index_batch.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(Interval), C.c_uint32, C.c_uint32, C.POINTER(FineOut)]
         L.smaltgpu_cands_geometry.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.smaltgpu_sort_u64_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
@@ -802,6 +820,57 @@ class Mapper:
                     run_off=runs["off"].copy(), run_n=runs["n"].copy(), run_mode=runs["mode"].copy(), hit_count=int(out.hit_count),
                     pool_cap=int(out.pool_cap), pool=arr(out.pool, np.uint64, min(int(out.hit_count), int(out.pool_cap))),
                     window=int(out.window), tab=int(out.tab), stride=int(stride))
+
+    @staticmethod
+    def pack_cands(cands):
+        """per-read lists of candidate dicts -> (offsets, smaltgpu_cand array) as align_cands_batch passes them on; a caller that
+        repeats a large batch converts it once and hands the pair in"""
+        n = len(cands)
+        co = (C.c_uint64 * (n + 1))()
+        flat = [c for lst in cands for c in lst]
+        t = 0
+        for i, lst in enumerate(cands):
+            co[i] = t
+            t += len(lst)
+        co[n] = t
+        arr = (Cand * max(1, len(flat)))()
+        for a, c in zip(arr, flat):
+            a.rs, a.re, a.qs, a.qe, a.band_l, a.band_r, a.sqidx = c["rs"], c["re"], c["qs"], c["qe"], c["band_l"], c["band_r"], c["sqidx"]
+            a.flags = (CAND_REVERSE if c["reverse"] else 0) | (CAND_ERR if c.get("err") else 0)
+            a.cover, a.swscor = c["cover"], c["swscor"]
+        return co, arr
+
+    def align_cands_batch(self, reads: Sequence[bytes], params: Params, cands, cover_deficit=None, prev_max=None, min_swatscor=None,
+                          raw_alignments: bool = False, antidiag: bool = False, allow_read_errors: bool = False):
+        """Stand-alone O1 + K3 driver (smaltgpu_align_cands_batch): k_replay and both passes of k_align over the caller's ranked
+        candidates and first-pass scores.  cands: per read a list of dicts of rs, re, qs, qe, band_l, band_r, sqidx, reverse, cover,
+        swscor and optionally err, or what pack_cands made of them; cover_deficit: per read (forward, reverse), default (0, 0).
+        -> (results, stats, cand_first flags per result, ctl dicts per read, number of reads deferred to the second pass)"""
+        bases, _, off = self._pack(reads, None)
+        n = len(reads)
+        co, arr = cands if isinstance(cands, tuple) else self.pack_cands(cands)
+        cdf = (C.c_uint32 * max(1, 2 * n))(*([x for pr_ in cover_deficit for x in pr_] if cover_deficit is not None else [0] * (2 * n)))
+        ctx = CallCtx()
+        keep = []
+        if prev_max is not None:
+            pm = (C.c_int32 * max(1, 2 * n))(*[x for pr_ in prev_max for x in pr_])
+            ctx.prev_max = pm
+            keep.append(pm)
+        if min_swatscor is not None:
+            ms = (C.c_int32 * max(1, n))(*min_swatscor)
+            ctx.min_swatscor = ms
+            keep.append(ms)
+        ctx.raw_alignments = 1 if raw_alignments else 0
+        out = AlignCandsOut()
+        rv = lib().smaltgpu_align_cands_batch(self.h, bases, None, off, n, C.byref(params), C.byref(ctx), co, arr, cdf,
+                                              ALIGN_CANDS_ANTIDIAG if antidiag else 0, C.byref(out))
+        if rv != 0 and not (allow_read_errors and rv in (ECAP, EINTERNAL, ESCORE) and out.batch.nreads == n):
+            _check(rv)
+        res, stats = self._unpack(out.batch)
+        cf = [[bool(out.batch.res[j].reverse & 2) for j in range(out.batch.res_off[i], out.batch.res_off[i + 1])] for i in range(n)]
+        ctl = [dict(max1=c.max1, max2=c.max2, n_scored=c.n_scored, bandwidth_min=c.bandwidth_min, min_swatscor=c.min_swatscor,
+                    scorlen_min=c.scorlen_min, go=c.go) for c in out.ctl[:n]]
+        return res, stats, cf, ctl, int(out.n_deferred)
 
     def fine_index_batch(self, intervals, grid: int = 0, guard: int = 0xA5C3E187):
         """Stand-alone k_fine_index (smaltgpu_fine_index_batch): intervals = per read a list of (sidx, lo, hi).  The position buffer

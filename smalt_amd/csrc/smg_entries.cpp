@@ -401,3 +401,87 @@ extern "C" int smaltgpu_gather_batch(smaltgpu_mapper *m, const uint8_t *const ba
   memcpy(dst_off, m->h_off.data(), ((size_t)nids + 1) * sizeof(uint64_t));
   return SMALTGPU_OK;
 }
+
+// O1 and the K3 driver on their own: reads staged and encoded as in a mapping call, the caller's candidates and first-pass scores
+// in place of what k_cands and the score kernels leave in the batch, then the tail of run_pipeline (launch_replay, both passes of
+// launch_align on the mapper's scratch, slots and capacities) and the ordinary fetch.  No rule of the stages is restated here: the
+// entry checks what production guarantees about a candidate and fills in the book-keeping fields.
+extern "C" int smaltgpu_align_cands_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
+                                          const smaltgpu_params *par, const smaltgpu_callctx *ctx, const uint64_t *cand_off, const smaltgpu_cand *cands,
+                                          const uint32_t *cover_deficit, uint32_t flags, smaltgpu_align_cands_out *out) {
+  static_assert(sizeof(smaltgpu_readctl) == sizeof(ReadCtl), "read control layout");
+  static_assert((uint32_t)SMALTGPU_CAND_REVERSE == (uint32_t)RCF_REVERSE, "strand flag");
+  if (!m || !bases || !read_off || !par || !cand_off || !cover_deficit || !out) return fail(SMALTGPU_EARG, "null argument");
+  if (nreads > m->max_reads || read_off[nreads] - read_off[0] > m->max_bases) return fail(SMALTGPU_EARG, "batch exceeds the mapper's capacity");
+  if (flags & ~(uint32_t)SMALTGPU_ALIGN_CANDS_ANTIDIAG) return fail(SMALTGPU_EARG, "unknown flags");
+  if (ctx && (ctx->iv_off || ctx->fine_index || ctx->seed_range)) return fail(SMALTGPU_EARG, "intervals, the on-the-fly index and seed ranges belong to the stages in front of this entry");
+  TRY(check_par(m, par));
+  if (par->rmapflg & SMALTGPU_FLG_CMPLXW) return fail(SMALTGPU_EARG, "complexity-weighted scores are not part of this entry");
+  const DevIndex &d = m->ix->d;
+  const std::vector<uint64_t> &sop = m->ix->sop;
+  for (uint32_t r = 0; r < nreads; r++) if (cand_off[r + 1] < cand_off[r] || read_off[r + 1] < read_off[r]) return fail(SMALTGPU_EARG, "offsets of read %u descend", r);
+  const uint64_t c0 = cand_off[0], tot = cand_off[nreads] - c0;
+  if (tot > m->b.rccap) return fail(SMALTGPU_EARG, "%llu candidates exceed the pool of %u", (unsigned long long)tot, m->b.rccap);
+  if (tot && !cands) return fail(SMALTGPU_EARG, "null argument");
+  std::vector<CandHdr> ch(nreads ? nreads : 1);
+  std::vector<RCand> rc(tot ? tot : 1);
+  memset((void *)ch.data(), 0, ch.size() * sizeof(CandHdr));
+  memset((void *)rc.data(), 0, rc.size() * sizeof(RCand));
+  for (uint32_t r = 0; r < nreads; r++) {
+    const uint64_t qlen = read_off[r + 1] - read_off[r];
+    const uint32_t nc = (uint32_t)(cand_off[r + 1] - cand_off[r]);
+    CandHdr &h = ch[r];
+    h.ncand = h.n_sort = h.n_mincover = h.n_reserved = nc;
+    h.rc_off = (uint32_t)(cand_off[r] - c0);
+    h.cover_deficit[0] = cover_deficit[2 * r]; h.cover_deficit[1] = cover_deficit[2 * r + 1];
+    for (uint32_t i = 0; i < nc; i++) {
+      const smaltgpu_cand &c = cands[cand_off[r] + i];
+      if (c.flags & ~(uint32_t)(SMALTGPU_CAND_REVERSE | SMALTGPU_CAND_ERR)) return fail(SMALTGPU_EARG, "candidate %u of read %u: unknown flags", i, r);
+      if (c.sqidx < -1 || c.sqidx >= d.nseq) return fail(SMALTGPU_EARG, "candidate %u of read %u: no sequence %d", i, r, c.sqidx);
+      const uint64_t slen = c.sqidx < 0 ? sop[(size_t)d.nseq] : sop[(size_t)c.sqidx + 1] - sop[(size_t)c.sqidx];
+      if (c.rs > c.re || c.re >= slen) return fail(SMALTGPU_EARG, "candidate %u of read %u: window outside its sequence", i, r);
+      if (c.swscor < 0 || (uint64_t)c.swscor > qlen * (uint64_t)par->match) return fail(SMALTGPU_EARG, "candidate %u of read %u: score %d outside 0 .. read length x match", i, r, c.swscor);
+      RCand &o = rc[h.rc_off + i];
+      o.rs = c.rs; o.re = c.re; o.qs = c.qs; o.qe = c.qe; o.band_l = c.band_l; o.band_r = c.band_r; o.sqidx = c.sqidx;
+      o.flags = (c.flags & SMALTGPU_CAND_REVERSE ? (uint32_t)RCF_REVERSE : 0u) | (c.flags & SMALTGPU_CAND_ERR ? (uint32_t)RCF_ERR : 0u) | (uint32_t)RCF_SCORED;
+      o.cover = c.cover; o.swscor = c.swscor; o.rid = r;
+    }
+  }
+  TRY(stage_reads(m, bases, quals, read_off, nreads));
+  CtxDev cd;
+  if (ctx) {
+    smaltgpu_callctx own = *ctx;
+    own.hitlist_len = nullptr;                             // sizes the hit lists of the seeding stage: nothing here reads it
+    TRY(upload_ctx(m, &own, nreads, &cd));
+  }
+  const Batch &b = m->b;
+  hipStream_t s = m->stream;
+  MapPar p;
+  TRY(begin_call(m, quals ? m->d_quals : nullptr, m->d_off, nreads, par, ctx ? &cd : nullptr, false, &p));
+  const uint32_t tot32 = (uint32_t)tot;
+  for (int i = 0; i <= T_REPLAY; i++) HIPCHK(hipEventRecord(m->ev[i], s));
+  int rv = launch_encode(s, m->d_bases, m->d_off, nreads, m->d_codes, m->d_codes_rc);
+  hipError_t he = hipSuccess;
+  if (nreads) {
+    he = hipMemsetAsync(b.hi, 0, 2 * (size_t)nreads * sizeof(HitInfoHdr), s);           // no seeding ran: nhit / nhit_tot come back 0
+    if (he == hipSuccess) he = hipMemcpyAsync(b.ch, ch.data(), (size_t)nreads * sizeof(CandHdr), hipMemcpyHostToDevice, s);
+    if (he == hipSuccess && tot) he = hipMemcpyAsync(b.rcpool, rc.data(), (size_t)tot * sizeof(RCand), hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(b.rc_count, &tot32, sizeof(tot32), hipMemcpyHostToDevice, s);
+  }
+  if (he == hipSuccess && !rv) rv = launch_replay(s, b, d, p);
+  if (he == hipSuccess) he = hipEventRecord(m->ev[T_ALIGN], s);
+  const int passflg = (int)(flags & SMALTGPU_ALIGN_CANDS_ANTIDIAG);
+  if (he == hipSuccess && !rv) rv = launch_align(s, b, d, p, m->align_scr, m->align_bytes, m->align_slots, m->wincap, m->dircap, m->rescap_slot, m->dstrcap_slot, 1 | passflg);
+  if (he == hipSuccess && !rv) rv = launch_align(s, b, d, p, m->align_scr2, m->align_bytes2, m->align_slots2, m->wincap, m->dircap2, m->rescap_slot2, m->dstrcap_slot2, 2 | passflg);
+  if (he == hipSuccess) he = hipEventRecord(m->ev[T_NUM], s);
+  const hipError_t hs = hipStreamSynchronize(s);           // before any return: the uploads read ch, rc and tot32
+  HIPCHK(he);
+  if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
+  HIPCHK(hs);
+  uint32_t nretry = 0;
+  TRY(fetch(m->h_ctl, b.ctl, nreads));
+  HIPCHK(hipMemcpy(&nretry, b.align_retry_n, sizeof(nretry), hipMemcpyDeviceToHost));
+  memset(out, 0, sizeof(*out));
+  out->ctl = (const smaltgpu_readctl *)m->h_ctl.data(); out->n_deferred = nretry;
+  return smaltgpu_fetch_results(m, &out->batch);
+}

@@ -79,6 +79,9 @@ def lib():
         L.or_map_cands.restype = C.POINTER(OrCand)
         L.or_map_cands.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.or_map_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.or_map_injected.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(OrParams), C.POINTER(OrCand), C.c_uint32,
+                                      C.POINTER(C.c_uint32), C.c_int]
+        L.or_map_thresholds.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.or_sw_full.restype = C.c_int
         L.or_sw_full.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int]
         L.or_sw_band_fast.argtypes = [C.POINTER(C.c_int), C.c_char_p, C.c_uint32, C.c_char_p, C.c_int, C.c_void_p, C.c_int,
@@ -148,6 +151,9 @@ class Mapper:
             lo = (C.c_uint32 * max(1, n_iv))(*[iv[1] for iv in intervals])
             hi = (C.c_uint32 * max(1, n_iv))(*[iv[2] for iv in intervals])
             rv = lib().or_map_single_restricted(self.m, bases, quals, len(bases), C.byref(params), n_iv, sx, lo, hi)
+        return rv, self._results()
+
+    def _results(self):
         n = C.c_int()
         dp = C.POINTER(C.c_uint8)()
         rp = lib().or_map_results(self.m, C.byref(n), C.byref(dp))
@@ -157,7 +163,31 @@ class Mapper:
             out.append(dict(reverse=r.reverse, score=r.swatscor, q_start=r.q_start, q_end=r.q_end, s_start=r.s_start,
                             s_end=r.s_end, sidx=r.sidx, diffstr=bytes(dp[r.stroffs:r.stroffs + r.strlen])))
         self.cand_first = [bool(rp[i].cand_first) for i in range(n.value)]
-        return rv, out
+        return out
+
+    def map_injected(self, bases: bytes, params, cands, cover_deficit=(0, 0), rescore=False, prevmax=None):
+        """or_map_injected: the read from the score pass on over the caller's candidates, dicts of rs, re, qs, qe, band_l, band_r,
+        sqidx, reverse, cover, swscor in rank order.  -> (return code, results as map() gives them, candidates as the oracle
+        holds them after the call: scored ones carry their score, the list ends where the cover cut ended it)."""
+        if prevmax is not None:
+            lib().or_map_set_prevmax(self.m, prevmax[0], prevmax[1])
+        n = len(cands)
+        arr = (OrCand * max(1, n))()
+        for a, c in zip(arr, cands):
+            a.flags, a.qs, a.qe, a.rs, a.re = (1 if c["reverse"] else 0), c["qs"], c["qe"], c["rs"], c["re"]
+            a.band_l, a.band_r, a.sqidx, a.swscor, a.cover = c["band_l"], c["band_r"], c["sqidx"], c.get("swscor", 0), c["cover"]
+        cdf = (C.c_uint32 * 2)(*cover_deficit)
+        rv = lib().or_map_injected(self.m, bases, len(bases), C.byref(params), arr, n, cdf, 1 if rescore else 0)
+        ns = C.c_int()
+        cp = lib().or_map_cands(self.m, C.byref(ns))
+        scored = [dict(swscor=cp[i].swscor, used_simd=cp[i].used_simd) for i in range(ns.value)]
+        return rv, self._results(), scored
+
+    def thresholds(self):
+        """(bandwidth_min, min_swatscor, scorlen_min, go) of the last read's threshold block"""
+        a = (C.c_int * 4)()
+        lib().or_map_thresholds(self.m, a)
+        return tuple(a)
 
     def hit_total(self, ktuple_maxhit):
         return int(lib().or_map_hit_total(self.m, ktuple_maxhit))
