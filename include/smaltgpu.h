@@ -682,6 +682,12 @@ typedef struct smaltgpu_hits_out {
  * for a batch above the mapper's capacity. */
 int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
                         const smaltgpu_params *par, uint32_t window, uint64_t pool_keys, smaltgpu_hits_out *out);
+/* How k_hits gathered the strands of the mapper's last call (a mapping call or smaltgpu_hits_batch).  windows (null, or
+ * [nstrands], nstrands <= 2 * reads of that call): per strand, bits 0..15 the windows it was gathered in (0: one gather, no keys,
+ * or a strand the kernel left alone), bits 16..31 those of them whose bound was raised above the safe one.  totals[0]: sorted
+ * strands gathered in several windows, [1]: their windows, [2]: their keys, [3]: keys reserved in the pool by the call.  All
+ * zero where the call did not run the kernel (restricted calls, mappers whose candidate stage keeps S3: max_read_len > 240). */
+int smaltgpu_hits_windows(smaltgpu_mapper *m, uint32_t nstrands, uint32_t *windows, uint64_t totals[4]);
 
 /* The on-the-fly index of the rescue round on its own (kernel k_fine_index): the intervals of nreads reads go up as in a call of
  * smaltgpu_map_batch_ctx with fine_index set, the mapper's position buffer (with one word behind the last read's slice) and

@@ -279,6 +279,7 @@ def lib():
                                             C.c_uint32, C.c_uint8, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.smaltgpu_hits_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.c_uint32, C.c_uint64,
                                           C.POINTER(HitsOut)]
+        L.smaltgpu_hits_windows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
         L.smaltgpu_align_cands_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.POINTER(CallCtx),
                                                  C.POINTER(C.c_uint64), C.POINTER(Cand), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AlignCandsOut)]
         L.smaltgpu_fine_index_batch.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(Interval), C.c_uint32, C.c_uint32, C.POINTER(FineOut)]
@@ -820,6 +821,18 @@ class Mapper:
                     run_off=runs["off"].copy(), run_n=runs["n"].copy(), run_mode=runs["mode"].copy(), hit_count=int(out.hit_count),
                     pool_cap=int(out.pool_cap), pool=arr(out.pool, np.uint64, min(int(out.hit_count), int(out.pool_cap))),
                     window=int(out.window), tab=int(out.tab), stride=int(stride))
+
+    def hits_windows(self, nstrands: int):
+        """How k_hits gathered the strands of the last call (smaltgpu_hits_windows) -> dict: windows[nstrands] (0: one gather or
+        none), raised[nstrands] (those of them whose bound was raised above the safe one), and the totals strands (gathered in
+        several windows), nwindows, keys (of those strands) and reserved (the pool cursor; 0 where the call ran no k_hits)."""
+        import numpy as np
+        win = np.zeros(max(1, nstrands), dtype=np.uint32)
+        tot = (C.c_uint64 * 4)()
+        _check(lib().smaltgpu_hits_windows(self.h, nstrands, win.ctypes.data_as(C.c_void_p), tot))
+        win = win[:nstrands]
+        return dict(windows=(win & 0xffff).astype(np.int64), raised=(win >> 16).astype(np.int64), strands=int(tot[0]), nwindows=int(tot[1]), keys=int(tot[2]),
+                    reserved=int(tot[3]))
 
     @staticmethod
     def pack_cands(cands):

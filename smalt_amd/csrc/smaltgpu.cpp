@@ -411,10 +411,14 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
       b.hitpool_cap = cap;
       DA(b.hitpool, cap);
       DA(m->b_hitrun, 2 * (size_t)max_batch_reads);
+      DA(m->b_hitwin, 2 * (size_t)max_batch_reads);
       const char *hw = getenv("SMALTGPU_HITS_WINDOW");
       m->hits_W = hw ? (uint32_t)atoi(hw) : 1024u;       // measured (1 M reads of the bench): 512: 195 ms, 768: 124 ms, 1024: 112 ms
       if (m->hits_W < 256) m->hits_W = 256;
       if (m->hits_W > 1024) m->hits_W = 1024;
+      const char *hf = getenv("SMALTGPU_HITS_FILL");          // tuning hook: fill target of a window in 1/1024 of its room, 0 = safe bounds only
+      m->hits_fill = hf ? (uint32_t)atoi(hf) : (uint32_t)HITS_FILL;
+      if (m->hits_fill > 1024) m->hits_fill = 1024;
       m->hits_wg = 256 * 24;                                     // persistent workgroups: more than can be resident at the smallest LDS block
     }
   }
@@ -606,7 +610,11 @@ int begin_call(smaltgpu_mapper *m, const uint8_t *d_quals, const uint64_t *d_off
   b.alloc_len = cx->alloc_len; b.seed_range = cx->seed_range;
   b.totals_only = totals_only ? 1u : 0u; b.raw_results = cx->raw;
   // S3 ahead of the candidate stage (plain calls of short-read mappers; restricted calls keep it inside k_cands)
-  b.hitrun = m->hits_W && !b.iv_off && !totals_only ? m->b_hitrun : nullptr;
+  // -- and only where the candidate stage's SPLIT instance consumes the runs (launch_cands: strides up to 255); at a stride of 256
+  // the stand-alone entry (smaltgpu_hits_batch) alone runs k_hits
+  b.hitrun = m->hits_W && hits_consumed(b.qmax) && !b.iv_off && !totals_only ? m->b_hitrun : nullptr;
+  b.hitwin = b.hitrun ? m->b_hitwin : nullptr;
+  m->hits_ran = b.hitrun != nullptr;
   if (b.fine_idx) p->flags |= FLG_NOSHRTINFO;            // initRMAPINFO, not the short form (rmap.c:2024)
   m->last_fine = b.fine_idx != nullptr;
   m->last_par = *p; m->last_n = n;
@@ -649,7 +657,7 @@ static int run_pipeline(smaltgpu_mapper *m, const uint8_t *d_bases, const uint8_
   HIPCHK(hipEventRecord(m->ev[T_SEED], s));
   if (!rv) rv = launch_seed(s, b, d, p, m->seed_scr, m->seed_bytes, m->seed_slots);
   HIPCHK(hipEventRecord(m->ev[T_HITS], s));
-  if (!rv && b.hitrun) rv = launch_hits(s, b, d, p, m->hits_W, m->cg.tab, m->hits_wg);
+  if (!rv && b.hitrun) rv = launch_hits(s, b, d, p, m->hits_W, m->cg.tab, m->hits_wg, m->hits_fill);
   HIPCHK(hipEventRecord(m->ev[T_CANDS], s));
   if (seed_only) {
     for (int i = T_CANDS + 1; i <= T_NUM; i++) HIPCHK(hipEventRecord(m->ev[i], s));

@@ -614,9 +614,13 @@ SMG_HD inline bool cands_v2_applicable(const MapPar &p, int k, int s, uint32_t q
 // the dependent index reads and LDS round trips the stage waits for.  What the fused form does not treat as a plain strand
 // (allocation-boundary protocol, hashhit.c:1497), restricted calls (rmapPair) and reads of 256 bases and more keep S3 inside
 // the candidate stage (HITRUN_NONE); so does any strand on which this function meets something it does not expect.
+// measured (1 M reads of the bench, k_hits per step): 0: 112.0 ms, 768: 107.6, 896: 100.6, 1024: 95.6; targets beyond the room
+// overshoot too often (1100: 96.1, 1180: 100.3)
+enum : uint32_t { HITS_FILL = 1024 };
 struct HitsScratch {
   uint8_t *lds; size_t lds_bytes;
   uint32_t W, tab;            // keys per window; entries of the per-list tables
+  uint32_t fill = HITS_FILL;  // a window below fill / 1024 of its room gets a second, higher bound (0: never; at most 1024)
 };
 SMG_HD inline size_t hits_lds_bytes(uint32_t W, uint32_t tab) { return (size_t)W * 8 + (((size_t)W + 64) * 2 + 15 & ~(size_t)15) + (size_t)5 * tab * 4 + 64; }
 
@@ -629,6 +633,7 @@ SMG_HD inline void stage_hits(const Batch &b, const DevIndex &ix, const MapPar &
   const bool seqbyseq = (p.flags & FLG_SEQBYSEQ) != 0;
   HitRun run;
   run.off = 0; run.n = 0; run.mode = HITRUN_NONE;
+  SMG_LANE0 { if (b.hitwin) b.hitwin[rs] = 0; }
   typedef typename ptr_of<uint64_t, true>::type P64;
   typedef typename ptr_of<uint16_t, true>::type P16;
   typedef typename ptr_of<uint32_t, true>::type P32;
@@ -760,80 +765,142 @@ SMG_HD inline void stage_hits(const Batch &b, const DevIndex &ix, const MapPar &
     sort_and_write(total, 0);
     t0 = phase_clock();
   } else {
-    // windows of ascending diagonal: every list contributes what lies below the window's bound (stage_cands_v2, mode 1)
-    uint32_t remaining = total, written = 0;
-    uint64_t prev_bound = 0;
+    // windows of ascending diagonal: every list contributes what lies below the window's bound (stage_cands_v2, mode 1).
+    // The safe bound is the least list element just past a list's quota: no list exceeds its quota, so the window fits, but as
+    // the minimum over all lists it leaves the window about a third full.  A window below the fill target therefore gets a
+    // second bound, extrapolated from the density of keys between the previous bound and the safe one, and an exact count of
+    // every list's remaining positions below it; it is taken when that count fits the window.  Any bound serves: the windows are
+    // prefixes, in key order, of what is left, and their concatenation is the sorted run.
+    uint32_t remaining = total, written = 0, nwin = 0, nraised = 0;
+    uint64_t prev_bound = 0, dprev = 0;
     const uint32_t room = W - nlist;
+    const uint32_t target = (uint32_t)(((uint64_t)room * x.fill) >> 10);
+    const uint64_t diagmask = (1ull << KEY_DIAGBITS) - 1ull;
+    auto bound_key = [&](uint32_t l, uint32_t at) -> uint64_t {          // (sequence, diagonal) of position `at` of list l
+      const uint32_t pos = ix.pos[g_poff[l] + at];
+      uint64_t kh = hit_diag_m(st != 0, pos, g_qo[l], smagic);
+      if (seqbyseq) kh |= (uint64_t)seq_of_pos(ix.seqlo, ix.nseq, pos) << KEY_DIAGBITS;
+      return kh;
+    };
+    // positions [0, hi) of list l from `cur` on that lie below the bound, of which the first lo are known to
+    auto count_below = [&](uint32_t l, uint32_t cur, uint64_t bound, uint32_t lo, uint32_t hi) -> uint32_t {
+      const uint32_t *pp = ix.pos + g_poff[l] + cur;
+      const int64_t qs = (int64_t)(g_qo[l] / (uint32_t)s);
+      const uint64_t db = bound & diagmask;
+      int64_t plim = st != 0 ? (int64_t)db - qs : (int64_t)db - (int64_t)(1ull << 32) + qs;
+      if (seqbyseq) {
+        const uint32_t sb = (uint32_t)(bound >> KEY_DIAGBITS);
+        if (sb >= (uint32_t)ix.nseq) plim = (int64_t)1 << 33;
+        else {
+          const int64_t slo = (int64_t)ix.seqlo[sb], shi = sb + 1 < (uint32_t)ix.nseq ? (int64_t)ix.seqlo[sb + 1] : ((int64_t)1 << 33);
+          plim = plim < slo ? slo : (plim > shi ? shi : plim);
+        }
+      } else if (bound == ~0ull) plim = (int64_t)1 << 33;
+      while (lo < hi) {                                  // eight-way search: seven independent index reads per round
+        const uint32_t n = hi - lo, step = (n + 7) >> 3;
+        uint32_t pv[7];
+#pragma unroll
+        for (int u = 0; u < 7; u++) { const uint32_t ip_ = lo + (uint32_t)(u + 1) * step - 1; pv[u] = ip_ < hi ? pp[ip_] : 0xffffffffu; }
+        uint32_t c = 0;
+#pragma unroll
+        for (int u = 0; u < 7; u++) c += ((lo + (uint32_t)(u + 1) * step - 1 < hi) && (int64_t)pv[u] < plim) ? 1u : 0u;
+        const uint32_t nlo = lo + c * step, piv = nlo + step - 1;
+        if (c < 7 && piv < hi) hi = piv;
+        lo = nlo;
+        if (step == 1 && c < 7) break;
+      }
+      return lo < hi ? lo : hi;
+    };
     while (remaining > 0) {
-      uint64_t bound = ~0ull;
+      uint64_t bound = ~0ull, first = ~0ull;
       SMG_PAR_CHUNKS(base, nlist) {
         const uint32_t l = base + SMG_LANE;
         if (l < nlist) {
           const uint32_t cur = g_cur[l], rem = g_len[l] - cur;
           if (rem) {
             const uint32_t t = (uint32_t)(((uint64_t)room * rem) / remaining) + 1;
-            if (t < rem) {
-              const uint32_t pos = ix.pos[g_poff[l] + cur + t];
-              uint64_t kh = hit_diag_m(st != 0, pos, g_qo[l], smagic);
-              if (seqbyseq) kh |= (uint64_t)seq_of_pos(ix.seqlo, ix.nseq, pos) << KEY_DIAGBITS;
-              if (kh < bound) bound = kh;
-            }
+            if (t < rem) { const uint64_t kh = bound_key(l, cur + t); if (kh < bound) bound = kh; }
+            if (nwin == 0 && target) { const uint64_t kh = bound_key(l, cur); if (kh < first) first = kh; }    // where the strand's keys begin
           }
         }
       }
       bound = wave_min_u64(bound);
-      SMG_PAR_CHUNKS(base, room + nlist) { const uint32_t i = base + SMG_LANE; if (i < room + nlist) marks[i] = 0; }
-      SMG_SYNC();
+      if (nwin == 0 && target) dprev = wave_min_u64(first) & diagmask;
+      // every list's count below the safe bound (no more than its quota): g_pfx holds the counts until the bound is settled
       uint32_t cnt_tot = 0;
       SMG_PAR_CHUNKS(base, nlist) {
         const uint32_t l = base + SMG_LANE;
-        uint32_t cnt = 0;
         if (l < nlist) {
           const uint32_t cur = g_cur[l], rem = g_len[l] - cur;
+          uint32_t cnt = 0;
           if (rem) {
             const uint32_t t = (uint32_t)(((uint64_t)room * rem) / remaining) + 1;
-            uint32_t lo = 0, hi = t < rem ? t : rem;
-            const uint32_t *pp = ix.pos + g_poff[l] + cur;
-            const int64_t qs = (int64_t)(g_qo[l] / (uint32_t)s);
-            const uint64_t db = bound & ((1ull << KEY_DIAGBITS) - 1ull);
-            int64_t plim = st != 0 ? (int64_t)db - qs : (int64_t)db - (int64_t)(1ull << 32) + qs;
-            if (seqbyseq) {
-              const uint32_t sb = (uint32_t)(bound >> KEY_DIAGBITS);
-              if (sb >= (uint32_t)ix.nseq) plim = (int64_t)1 << 33;
-              else {
-                const int64_t slo = (int64_t)ix.seqlo[sb], shi = sb + 1 < (uint32_t)ix.nseq ? (int64_t)ix.seqlo[sb + 1] : ((int64_t)1 << 33);
-                plim = plim < slo ? slo : (plim > shi ? shi : plim);
-              }
-            } else if (bound == ~0ull) plim = (int64_t)1 << 33;
-            while (lo < hi) {                                  // eight-way search: seven independent index reads per round
-              const uint32_t n = hi - lo, step = (n + 7) >> 3;
-              uint32_t pv[7];
-#pragma unroll
-              for (int u = 0; u < 7; u++) { const uint32_t ip_ = lo + (uint32_t)(u + 1) * step - 1; pv[u] = ip_ < hi ? pp[ip_] : 0xffffffffu; }
-              uint32_t c = 0;
-#pragma unroll
-              for (int u = 0; u < 7; u++) c += ((lo + (uint32_t)(u + 1) * step - 1 < hi) && (int64_t)pv[u] < plim) ? 1u : 0u;
-              const uint32_t nlo = lo + c * step, piv = nlo + step - 1;
-              if (c < 7 && piv < hi) hi = piv;
-              lo = nlo;
-              if (step == 1 && c < 7) break;
-            }
-            cnt = lo < hi ? lo : hi;
+            cnt = count_below(l, cur, bound, 0, t < rem ? t : rem);
           }
+          g_pfx[l] = cnt;
+          cnt_tot += cnt;
         }
+      }
+      cnt_tot = wave_sum_u32(cnt_tot);
+      if (cnt_tot > W || cnt_tot == 0) { bad = true; break; }
+      if (bound != ~0ull && cnt_tot < target && (bound & diagmask) > dprev) {
+        // the second bound: as far beyond the previous one as the fill target lies beyond this count, along the diagonal (which
+        // runs on through the sequences, as the k-mer serials do); sequence by sequence it takes the sequence its diagonal lies in
+        uint64_t d2 = dprev + ((bound & diagmask) - dprev) * target / cnt_tot;
+        if (d2 > diagmask) d2 = diagmask;
+        uint64_t bound2 = d2;
+        if (seqbyseq) {
+          const uint64_t offs = st != 0 ? 0ull : 1ull << 32;
+          uint64_t p2 = d2 > offs ? d2 - offs : 0ull;
+          if (p2 > 0xffffffffull) p2 = 0xffffffffull;
+          uint32_t sb2 = seq_of_pos(ix.seqlo, ix.nseq, (uint32_t)p2);
+          const uint32_t sb1 = (uint32_t)(bound >> KEY_DIAGBITS);
+          if (sb2 < sb1) sb2 = sb1;
+          bound2 = ((uint64_t)sb2 << KEY_DIAGBITS) | d2;
+        }
+        if (bound2 > bound) {
+          // exact counts below it, over the rest of every list: the search starts at the count known for the safe bound and ends
+          // where the list alone would overfill the window.  They wait in `marks` (not in use yet) until their total is known.
+          const uint32_t over = W - cnt_tot + 1;
+          uint32_t tot2 = 0;
+          SMG_PAR_CHUNKS(base, nlist) {
+            const uint32_t l = base + SMG_LANE;
+            if (l < nlist) {
+              const uint32_t cur = g_cur[l], rem = g_len[l] - cur, c1 = g_pfx[l];
+              const uint32_t c2 = c1 < rem ? count_below(l, cur, bound2, c1, rem - c1 > over ? c1 + over : rem) : c1;
+              marks[l] = (uint16_t)c2;
+              tot2 += c2;
+            }
+          }
+          tot2 = wave_sum_u32(tot2);
+          if (tot2 <= W) {                                   // (else the safe bound's counts stand)
+            SMG_PAR_CHUNKS(base, nlist) { const uint32_t l = base + SMG_LANE; if (l < nlist) g_pfx[l] = marks[l]; }
+            bound = bound2; cnt_tot = tot2; nraised++;
+          }
+          SMG_SYNC();
+        }
+      }
+      nwin++;
+      dprev = bound & diagmask;
+      SMG_PAR_CHUNKS(base, cnt_tot) { const uint32_t i = base + SMG_LANE; if (i < cnt_tot) marks[i] = 0; }
+      SMG_SYNC();
+      // counts -> exclusive prefix, and a mark where every list's keys begin
+      uint32_t run_tot = 0;
+      SMG_PAR_CHUNKS(base, nlist) {
+        const uint32_t l = base + SMG_LANE;
+        const uint32_t cnt = l < nlist ? g_pfx[l] : 0u;
         uint32_t incl = cnt;
 #if defined(__HIP_DEVICE_COMPILE__)
         for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += v; }
 #endif
-        if (l < nlist) { g_pfx[l] = cnt_tot + incl - cnt; if (cnt && cnt_tot + incl - cnt < room + nlist) marks[cnt_tot + incl - cnt] = (uint16_t)(l + 1); }
+        if (l < nlist) { g_pfx[l] = run_tot + incl - cnt; if (cnt && run_tot + incl - cnt < room + nlist) marks[run_tot + incl - cnt] = (uint16_t)(l + 1); }
 #if defined(__HIP_DEVICE_COMPILE__)
-        cnt_tot += (uint32_t)__shfl((int)incl, 63);
+        run_tot += (uint32_t)__shfl((int)incl, 63);
 #else
-        cnt_tot += incl;
+        run_tot += incl;
 #endif
       }
       SMG_SYNC();
-      if (cnt_tot > W || cnt_tot == 0) { bad = true; break; }
       const uint32_t sq_lo = seqbyseq ? (uint32_t)(prev_bound >> KEY_DIAGBITS) : 0u;
       uint32_t sq_hi = seqbyseq ? (uint32_t)(bound >> KEY_DIAGBITS) : 0u;
       if (sq_hi >= (uint32_t)ix.nseq) sq_hi = (uint32_t)ix.nseq - 1;
@@ -879,6 +946,7 @@ SMG_HD inline void stage_hits(const Batch &b, const DevIndex &ix, const MapPar &
       written += cnt_tot;
     }
     if (!bad && written != total) bad = true;
+    SMG_LANE0 { if (b.hitwin) b.hitwin[rs] = nwin | nraised << 16; }
   }
   if (!bad) run.mode = HITRUN_SORTED;          // (else the candidate stage does this strand itself; the pool space stays unused)
   SMG_LANE0 { b.hitrun[rs] = run; }

@@ -231,10 +231,12 @@ extern "C" int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, con
   TRY(begin_call(m, quals ? m->d_quals : nullptr, m->d_off, nreads, par, nullptr, false, &p));
   m->fetch_open = false;
   Batch hb = b;
+  m->hits_ran = true;
+  hb.hitrun = m->b_hitrun; hb.hitwin = m->b_hitwin;       // (a mapping call of a mapper with a stride of 256 leaves k_hits out: begin_call)
   hb.hitpool_cap = cap;                                   // this call only: the kernels take a copy of the batch
   int rv = launch_encode(s, m->d_bases, m->d_off, nreads, m->d_codes, m->d_codes_rc);
   if (!rv) rv = launch_seed(s, hb, d, p, m->seed_scr, m->seed_bytes, m->seed_slots);
-  if (!rv) rv = launch_hits(s, hb, d, p, W, m->cg.tab, m->hits_wg);
+  if (!rv) rv = launch_hits(s, hb, d, p, W, m->cg.tab, m->hits_wg, m->hits_fill);
   if (rv) return fail(SMALTGPU_ENODEV, "kernel launch failed: %s", hipGetErrorString((hipError_t)rv));
   HIPCHK(hipStreamSynchronize(s));
   smaltgpu_mapper::HitsHost &h = m->hh;
@@ -258,6 +260,28 @@ extern "C" int smaltgpu_hits_batch(smaltgpu_mapper *m, const uint8_t *bases, con
   out->n_seeds = h.n_seeds.data(); out->seed_rank = h.seed_rank.data(); out->status = h.status.data();
   out->seeds = (const smaltgpu_hit_seed *)h.seeds.data(); out->qmask = h.qmask.data(); out->runs = (const smaltgpu_hit_run *)h.runs.data();
   out->hit_count = count; out->pool_cap = cap; out->pool = h.pool.data();
+  return SMALTGPU_OK;
+}
+
+// How k_hits gathered the strands of the mapper's last call (a mapping call or smaltgpu_hits_batch), from the table the kernel leaves
+extern "C" int smaltgpu_hits_windows(smaltgpu_mapper *m, uint32_t nstrands, uint32_t *windows, uint64_t totals[4]) {
+  if (!m || !totals) return fail(SMALTGPU_EARG, "null argument");
+  if (nstrands > 2 * (uint64_t)m->last_n) return fail(SMALTGPU_EARG, "the last call held %u strands", 2 * m->last_n);
+  totals[0] = totals[1] = totals[2] = totals[3] = 0;
+  if (windows) memset(windows, 0, (size_t)nstrands * sizeof(uint32_t));
+  if (!m->hits_ran || !nstrands) return SMALTGPU_OK;
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  std::vector<uint32_t> win(nstrands);
+  std::vector<HitRun> runs(nstrands);
+  unsigned long long count = 0;
+  HIPCHK(hipMemcpy(win.data(), m->b_hitwin, (size_t)nstrands * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(runs.data(), m->b_hitrun, (size_t)nstrands * sizeof(HitRun), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&count, m->b.hit_count, sizeof(count), hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < nstrands; i++)
+    if ((win[i] & 0xffffu) && runs[i].mode == HITRUN_SORTED) { totals[0]++; totals[1] += win[i] & 0xffffu; totals[2] += runs[i].n; }
+  totals[3] = count;
+  if (windows) memcpy(windows, win.data(), (size_t)nstrands * sizeof(uint32_t));
   return SMALTGPU_OK;
 }
 

@@ -36,7 +36,7 @@ inline size_t cand_slot_bytes(const CandGeom &g, uint32_t qmax, int s) {
 }
 // LDS working set of the candidate stage when S3 runs inside it (k_cands<false>, k_cands<true>): hits and per-list tables
 inline uint32_t cands_lds_bytes(const CandGeom &g) { return (uint32_t)(((strand_work_bytes<uint16_t>(g.lds_hits) + 15) & ~(size_t)15) + (size_t)5 * g.tab * 4); }
-int launch_hits(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t W, uint32_t tab, uint32_t nwg);
+int launch_hits(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t W, uint32_t tab, uint32_t nwg, uint32_t fill);
 int launch_cands(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint8_t *scratch, uint32_t nslots, const CandGeom &g);
 int launch_replay(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p);
 // cplx: table of logarithms and lambda; needed (and read) only when p.flags has FLG_CMPLXW

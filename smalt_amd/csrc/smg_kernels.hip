@@ -135,7 +135,7 @@ int launch_fine_index(hipStream_t s, const Batch &b, const DevIndex &ix, uint32_
 // S3 ahead of the candidate stage: one wave per read strand (stage_hits, smg_cands.hpp); 4 waves per SIMD by registers,
 // the LDS block (window keys + list tables) sized by the launcher for as many
 template <int WAVES>
-__global__ void __launch_bounds__(64, WAVES) k_hits(Batch b, DevIndex ix, MapPar p, uint32_t W, uint32_t tab, uint32_t lds_bytes) {
+__global__ void __launch_bounds__(64, WAVES) k_hits(Batch b, DevIndex ix, MapPar p, uint32_t W, uint32_t tab, uint32_t lds_bytes, uint32_t fill) {
   extern __shared__ __align__(16) uint8_t lds[];
   unsigned long long ph[4] = {0, 0, 0, 0};
   __shared__ uint32_t qslot;
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(64, WAVES) k_hits(Batch b, DevIndex ix, MapPar
     __syncthreads();
   }
   HitsScratch x;
-  x.lds = lds + LDS_GUARD; x.lds_bytes = lds_bytes; x.W = W; x.tab = tab;
+  x.lds = lds + LDS_GUARD; x.lds_bytes = lds_bytes; x.W = W; x.tab = tab; x.fill = fill < 1024u ? fill : 1024u;
   const uint32_t nitem = 2 * b.nreads;
   for (uint32_t it = next_item(b.hits_cursor, &qslot); it < nitem; it = next_item(b.hits_cursor, &qslot)) {
     stage_hits(b, ix, p, it >> 1, it & 1u, x, ph);
@@ -1807,15 +1807,15 @@ int launch_seed(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar 
   return 0;
 }
 
-int launch_hits(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t W, uint32_t tab, uint32_t nwg) {
+int launch_hits(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar &p, uint32_t W, uint32_t tab, uint32_t nwg, uint32_t fill) {
   if (!b.nreads || !b.hitrun) return 0;
   const uint32_t lds_bytes = (uint32_t)((hits_lds_bytes(W, tab) + 15) & ~(size_t)15);
   const size_t seq_bytes = (ix.nseq > 0 && ix.nseq < 512) ? (((size_t)ix.nseq + 1) * 4 + 15) & ~(size_t)15 : 0;
   uint32_t grid = 2 * b.nreads < nwg ? 2 * b.nreads : nwg;
   static const int waves = getenv("SMALTGPU_HITS_WAVES") ? atoi(getenv("SMALTGPU_HITS_WAVES")) : 3;      // tuning hook (3 waves per SIMD: 148 registers, no spills; 2 and 4 measured the same)
-  if (waves == 3) hipLaunchKernelGGL(k_hits<3>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, W, tab, lds_bytes);
-  else if (waves == 2) hipLaunchKernelGGL(k_hits<2>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, W, tab, lds_bytes);
-  else hipLaunchKernelGGL(k_hits<4>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, W, tab, lds_bytes);
+  if (waves == 3) hipLaunchKernelGGL(k_hits<3>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, W, tab, lds_bytes, fill);
+  else if (waves == 2) hipLaunchKernelGGL(k_hits<2>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, W, tab, lds_bytes, fill);
+  else hipLaunchKernelGGL(k_hits<4>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, W, tab, lds_bytes, fill);
   SMG_LAUNCH_CHECK();
   return 0;
 }
@@ -1825,8 +1825,8 @@ int launch_cands(hipStream_t s, const Batch &b, const DevIndex &ix, const MapPar
   uint32_t grid = b.nreads < nslots ? b.nreads : nslots;
   const uint32_t lds_bytes = cands_lds_bytes(g);
   const size_t seq_bytes = (ix.nseq > 0 && ix.nseq < 512) ? (((size_t)ix.nseq + 1) * 4 + 15) & ~(size_t)15 : 0;     // LDS copy of seqlo
-  if (b.qmax > 255) hipLaunchKernelGGL(k_cands<true>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, scratch, g, lds_bytes);
-  else if (b.hitrun) {
+  if (!hits_consumed(b.qmax)) hipLaunchKernelGGL(k_cands<true>, dim3(grid), dim3(64), lds_bytes + LDS_GUARD + seq_bytes, s, b, ix, p, scratch, g, lds_bytes);
+  else if (b.hitrun) {                                   // (begin_call sets it by hits_consumed(qmax) alone)
     // S3 ran ahead (k_hits): no per-list tables in this kernel's LDS block, and (tuning hook) three waves per SIMD
     static const int waves3 = getenv("SMALTGPU_CANDS_WAVES") && atoi(getenv("SMALTGPU_CANDS_WAVES")) == 3;
     const uint32_t lb = (uint32_t)((strand_work_bytes<uint16_t>(g.lds_hits) + 15) & ~(size_t)15);

@@ -83,6 +83,9 @@ struct smaltgpu_mapper {
   uint64_t *d_off = nullptr;
   uint32_t *d_ids = nullptr;                  // read ids of a round gathered from resident batches (smaltgpu_map_batch_ctx_resident)
   uint32_t hits_W = 0, hits_wg = 0;          // k_hits: keys per window, workgroups (0: S3 stays inside k_cands)
+  bool hits_ran = false;                     // the last call launched k_hits (smaltgpu_hits_windows)
+  uint32_t hits_fill = 0;                    // k_hits: fill target of a window (HitsScratch::fill)
+  uint32_t *b_hitwin = nullptr;               // windows per strand (Batch::hitwin), allocated with the run table
   HitRun *b_hitrun = nullptr;                 // the run table; Batch::hitrun is set per call (begin_call): null where k_hits does not run
   Batch b;
   // Counters of a batch, one 128-byte line each: atomics on one line are served one after the other (2 ns each), and the pool cursors,

@@ -22,6 +22,10 @@ enum : uint32_t { HITRUN_NONE = 0,      // the candidate stage gathers and sorts
                   HITRUN_SORTED = 1,    // hitpool[off .. off + n) holds the strand's keys in ascending order
                   HITRUN_OVERFLOW = 2 };// the pool was full: the read takes SMG_ERR_CAP (re-mapped in a smaller batch)
 
+// Strides up to 255 read offsets take the lean instances of the candidate kernel, and only there does its SPLIT instance consume
+// the runs of k_hits (launch_cands): the one predicate for running k_hits ahead of a mapping call
+SMG_HD inline bool hits_consumed(uint32_t qmax) { return qmax <= 255u; }
+
 struct Batch {                          // one block of reads resident in HBM
   uint32_t nreads, qmax;                // qmax: stride of the per-read-strand arrays (>= longest read + 1)
   const uint8_t *codes;                 // 3-bit codes of all reads, forward orientation, concatenated
@@ -64,6 +68,7 @@ struct Batch {                          // one block of reads resident in HBM
   HitRun *hitrun;                       // [2 * nreads]
   uint64_t *hitpool; uint64_t hitpool_cap; unsigned long long *hit_count;    // bump-allocated sorted keys
   uint32_t *hits_cursor;                // work-queue cursor of k_hits
+  uint32_t *hitwin;                     // [2 * nreads] or null: windows a strand was gathered in (0: one gather), << 16 those whose bound was raised
 };
 
 // Capacity and ceiling of the reference's hit list for a read of qlen bases (initHitList, hashhit.c:1262-1288).  The ceiling
