@@ -615,7 +615,8 @@ SMG_HD inline bool cands_v2_applicable(const MapPar &p, int k, int s, uint32_t q
 // (allocation-boundary protocol, hashhit.c:1497), restricted calls (rmapPair) and reads of 256 bases and more keep S3 inside
 // the candidate stage (HITRUN_NONE); so does any strand on which this function meets something it does not expect.
 // measured (1 M reads of the bench, k_hits per step): 0: 112.0 ms, 768: 107.6, 896: 100.6, 1024: 95.6; targets beyond the room
-// overshoot too often (1100: 96.1, 1180: 100.3)
+// overshoot too often (1100: 96.1, 1180: 100.3).  Again with the one-compare exchanges of the register sort (keep_side_u64), two
+// rounds: 0: 97.4 / 98.4 ms, 768: 92.7 / 92.6, 896: 87.3 / 87.2, 1024: 83.4 / 83.4 -- a cheaper sort does not move the optimum
 enum : uint32_t { HITS_FILL = 1024 };
 struct HitsScratch {
   uint8_t *lds; size_t lds_bytes;

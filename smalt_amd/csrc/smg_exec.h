@@ -198,6 +198,14 @@ __device__ inline uint64_t shfl_xor_u64(uint64_t v, int mask) {
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
   return ((uint64_t)hi << 32) | lo;
 }
+// One side of a comparator whose two keys sit in two lanes: v is the lane's own key, o the partner's; the lower lane keeps the
+// smaller key, the upper lane the larger one.  One 64-bit compare, turned round on the upper side: take = (o < v) != upper.
+// That differs from "o < v below, o > v above" only where o == v, and there taking o or keeping v leaves the same bits in the
+// register, so it is the same network; the ~0 padding beyond n is just another equal key (a real key ~0 beside it included).
+// Written with two compares and a choice between them, the compiler turns both conditions into 0/1 values, selects one, masks
+// and compares again: nine vector instructions per exchange.  This form is one v_cmp_lt_u64, one s_xor_b64 with the step's lane
+// mask (scalar unit) and the two selects of the key's halves (profiles/hits_sort_exchange_static.txt).
+__device__ inline uint64_t keep_side_u64(uint64_t v, uint64_t o, bool upper) { return ((o < v) != upper) ? o : v; }
 template <int E, class P>
 __device__ inline void wave_sort_u64_reg(P a, uint32_t n) {
   if (n < 2) return;
@@ -215,12 +223,12 @@ __device__ inline void wave_sort_u64_reg(P a, uint32_t n) {
       }
     } else {                                           // mirror step across lanes
       const int m = k / E - 1;
-      const bool lower = (lane & (uint32_t)(k / (2 * E))) == 0;
+      const bool upper = (lane & (uint32_t)(k / (2 * E))) != 0;
       uint64_t pv[E];
 #pragma unroll
       for (int r = 0; r < E; r++) pv[r] = shfl_xor_u64(v[E - 1 - r], m);
 #pragma unroll
-      for (int r = 0; r < E; r++) { const bool take = lower ? (pv[r] < v[r]) : (pv[r] > v[r]); v[r] = take ? pv[r] : v[r]; }
+      for (int r = 0; r < E; r++) { v[r] = keep_side_u64(v[r], pv[r], upper); }
     }
 #pragma unroll
     for (int j = k / 4; j >= 1; j >>= 1) {
@@ -231,9 +239,9 @@ __device__ inline void wave_sort_u64_reg(P a, uint32_t n) {
         }
       } else {
         const int m = j / E;
-        const bool lower = (lane & (uint32_t)m) == 0;
+        const bool upper = (lane & (uint32_t)m) != 0;
 #pragma unroll
-        for (int r = 0; r < E; r++) { const uint64_t o = shfl_xor_u64(v[r], m); const bool take = lower ? (o < v[r]) : (o > v[r]); v[r] = take ? o : v[r]; }
+        for (int r = 0; r < E; r++) { v[r] = keep_side_u64(v[r], shfl_xor_u64(v[r], m), upper); }
       }
     }
   }
@@ -268,9 +276,9 @@ __device__ inline void sort_chunk_1024(P a, uint32_t base, uint32_t n) {
     }
 #pragma unroll
     for (int j = 32; j >= 1; j >>= 1) {
-      const bool lower = (lane & (uint32_t)j) == 0;
+      const bool upper = (lane & (uint32_t)j) != 0;
 #pragma unroll
-      for (int r = 0; r < E; r++) { const uint64_t o = shfl_xor_u64(v[r], j); const bool take = lower ? (o < v[r]) : (o > v[r]); v[r] = take ? o : v[r]; }
+      for (int r = 0; r < E; r++) { v[r] = keep_side_u64(v[r], shfl_xor_u64(v[r], j), upper); }
     }
 #pragma unroll
     for (int r = 0; r < E; r++) { const uint32_t idx = base + (uint32_t)r * 64u + lane; if (idx < n) a[idx] = v[r]; }
@@ -286,12 +294,12 @@ __device__ inline void sort_chunk_1024(P a, uint32_t base, uint32_t n) {
       }
     } else {
       const int m = k / E - 1;
-      const bool lower = (lane & (uint32_t)(k / (2 * E))) == 0;
+      const bool upper = (lane & (uint32_t)(k / (2 * E))) != 0;
       uint64_t pv[E];
 #pragma unroll
       for (int r = 0; r < E; r++) pv[r] = shfl_xor_u64(v[E - 1 - r], m);
 #pragma unroll
-      for (int r = 0; r < E; r++) { const bool take = lower ? (pv[r] < v[r]) : (pv[r] > v[r]); v[r] = take ? pv[r] : v[r]; }
+      for (int r = 0; r < E; r++) { v[r] = keep_side_u64(v[r], pv[r], upper); }
     }
 #pragma unroll
     for (int j = k / 4; j >= 1; j >>= 1) {
@@ -302,9 +310,9 @@ __device__ inline void sort_chunk_1024(P a, uint32_t base, uint32_t n) {
         }
       } else {
         const int m = j / E;
-        const bool lower = (lane & (uint32_t)m) == 0;
+        const bool upper = (lane & (uint32_t)m) != 0;
 #pragma unroll
-        for (int r = 0; r < E; r++) { const uint64_t o = shfl_xor_u64(v[r], m); const bool take = lower ? (o < v[r]) : (o > v[r]); v[r] = take ? o : v[r]; }
+        for (int r = 0; r < E; r++) { v[r] = keep_side_u64(v[r], shfl_xor_u64(v[r], m), upper); }
       }
     }
   }
