@@ -156,13 +156,26 @@ int smaltgpu_index_save(const smaltgpu_index *ix, const char *prefix);
  * reference's: a prompt counts only as the first byte of a line and not on the line behind a header line, every other byte of the
  * sequence lines that is not white space is a base, the name of a sequence is its whole header line with each run of white space
  * cut down to its first character.  SMALTGPU_EARG with a message that names the cause: an empty text, a text that does not
- * begin with a prompt, a FASTQ-format reference ('@' or '+' prompts: the reference program takes those, this path does not), and
+ * begin with a prompt, a FASTQ-format reference ('@' or '+' prompts: taken by the _ex calls with SMALTGPU_TEXT_FASTQ, below), and
  * what smaltgpu_index_build_device refuses (a sequence shorter than the word length, ...).  parse_ms / build_ms (may be NULL):
  * device time of the parse and of the construction.  SMALTGPU_FASTA_BLOCK in the environment (read once per call; a test hook):
  * bytes of text per workgroup, at least 64 (default 256 KiB); small values are for small texts: the block size is doubled
  * until the text has at most 2^20 blocks. ---- */
 int smaltgpu_index_build_text(smaltgpu_index **out, int device, const char *text, uint64_t text_len, int32_t k, int32_t s, float *parse_ms,
                               float *build_ms);
+/* The same with flags.  0: the call above.  SMALTGPU_TEXT_FASTQ: a text with '@' or '+' prompts is read as the reference program
+ * reads it (seqFastqRead sequence.c:1960-1990, readQual :1743-1772; the rules are stated in smg_fastq_ref.hpp): '@' opens a record
+ * like '>'; a '+' prompt behind a sequence opens its quality section, which ends at the first prompt once it holds as many
+ * characters as the sequence has bases -- lines that begin with '@', '+' or '>' before that are quality data; a segment behind
+ * any other '+' prompt is dropped; a sequence that no '+' follows is a FASTA record, and a file may mix both kinds.  Qualities
+ * are discarded.  A quality section of another length than its sequence is SMALTGPU_EARG "wrong FASTQ/FASTA format" with the
+ * record's name, the number of its prompt in the text and its byte offset.  A text without such prompts takes the route and the
+ * time of the call above.  A text whose first prompt is '@' or '+' is walked record by record on the device (smg_fastq_ref.hip);
+ * one that begins with '>' and has such prompts further down is found out by the first route's output pass and walked then,
+ * and parse_ms is the time of the walk's route alone.  SMALTGPU_FASTA_BLOCK holds for both routes. */
+#define SMALTGPU_TEXT_FASTQ 1u
+int smaltgpu_index_build_text_ex(smaltgpu_index **out, int device, const char *text, uint64_t text_len, int32_t k, int32_t s, float *parse_ms,
+                                 float *build_ms, uint32_t flags);
 /* The parse alone, back in host memory.  The view's arrays belong to `fa` and hold until smaltgpu_fasta_free. */
 typedef struct smaltgpu_fasta smaltgpu_fasta;
 typedef struct smaltgpu_fasta_view {
@@ -172,9 +185,11 @@ typedef struct smaltgpu_fasta_view {
   const uint8_t *bases;                /* the sequences concatenated, letters as in the file */
   float upload_ms;                     /* host time of the copy of the text to the device */
   float parse_ms;                      /* device time of the three steps together ... */
-  float step_ms[3];                    /* ... and of each: block summaries, their composition, the output pass */
+  float step_ms[3];                    /* ... and of each: block summaries, their composition, the output pass (a text with FASTQ
+                                          records: candidates and prefix counts, the walk over the records, the output pass) */
 } smaltgpu_fasta_view;
 int smaltgpu_fasta_parse(smaltgpu_fasta **out, int device, const char *text, uint64_t text_len, smaltgpu_fasta_view *view);
+int smaltgpu_fasta_parse_ex(smaltgpu_fasta **out, int device, const char *text, uint64_t text_len, smaltgpu_fasta_view *view, uint32_t flags);
 void smaltgpu_fasta_free(smaltgpu_fasta *fa);
 
 /* ---- mapper (replaces rmapCreate rmap.c:1511 / rmapDelete :1597) ---- */

@@ -216,6 +216,8 @@ def lib():
         L.smaltgpu_index_build_text.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                                 C.POINTER(C.c_float)]
         L.smaltgpu_fasta_parse.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_uint64, C.POINTER(FastaView)]
+        L.smaltgpu_index_build_text_ex.argtypes = L.smaltgpu_index_build_text.argtypes + [C.c_uint32]
+        L.smaltgpu_fasta_parse_ex.argtypes = L.smaltgpu_fasta_parse.argtypes + [C.c_uint32]
         L.smaltgpu_fasta_free.argtypes = [C.c_void_p]
         L.smaltgpu_index_info.argtypes = [C.c_void_p, C.POINTER(IndexDesc)]
         L.smaltgpu_params_default.argtypes = [C.POINTER(Params), C.c_void_p]
@@ -337,12 +339,19 @@ def _fasta_text(path_or_bytes) -> bytes:
     return raw
 
 
-def parse_fasta(path_or_bytes, device: int = 0):
+TEXT_FASTQ = 1                         # SMALTGPU_TEXT_FASTQ
+
+
+def parse_fasta(path_or_bytes, device: int = 0, fastq: bool = False):
     """The reference sequences of a FASTA text as `smalt index` reads them, parsed on the device (smaltgpu_fasta_parse):
-    -> (names, sequences, times) with times = dict(upload_ms, parse_ms, step_ms).  Names are the whole header lines."""
+    -> (names, sequences, times) with times = dict(upload_ms, parse_ms, step_ms).  Names are the whole header lines.
+    fastq: a text with '@' or '+' prompts is read as FASTQ records, qualities discarded (smaltgpu_fasta_parse_ex)."""
     text = _fasta_text(path_or_bytes)
     h, v = C.c_void_p(), FastaView()
-    _check(lib().smaltgpu_fasta_parse(C.byref(h), device, text, len(text), C.byref(v)))
+    if fastq:
+        _check(lib().smaltgpu_fasta_parse_ex(C.byref(h), device, text, len(text), C.byref(v), TEXT_FASTQ))
+    else:
+        _check(lib().smaltgpu_fasta_parse(C.byref(h), device, text, len(text), C.byref(v)))
     try:
         names = [v.names[i].decode("latin-1") for i in range(v.nseq)]
         base = C.addressof(v.bases.contents) if v.nseq else 0
@@ -469,14 +478,18 @@ class Index:
         return ix
 
     @classmethod
-    def from_fasta(cls, path_or_bytes, k: int = 13, s: int = 6, device: int = 0) -> "Index":
+    def from_fasta(cls, path_or_bytes, k: int = 13, s: int = 6, device: int = 0, fastq: bool = False) -> "Index":
         """Build the index image from the text of a FASTA file (`smalt index`): a path (plain or gzipped) or the text itself.
         The text is parsed on the device by the reference's rules (smaltgpu_index_build_text); `parse_ms` and `build_ms` hold
-        the device times of the parse and of the construction."""
+        the device times of the parse and of the construction.  fastq: a text with '@' or '+' prompts is read as FASTQ
+        records, as `smalt index` does (smaltgpu_index_build_text_ex with SMALTGPU_TEXT_FASTQ); without it such a text is refused."""
         text = _fasta_text(path_or_bytes)
         h = C.c_void_p()
         pms, bms = C.c_float(0.0), C.c_float(0.0)
-        _check(lib().smaltgpu_index_build_text(C.byref(h), device, text, len(text), k, s, C.byref(pms), C.byref(bms)))
+        if fastq:
+            _check(lib().smaltgpu_index_build_text_ex(C.byref(h), device, text, len(text), k, s, C.byref(pms), C.byref(bms), TEXT_FASTQ))
+        else:
+            _check(lib().smaltgpu_index_build_text(C.byref(h), device, text, len(text), k, s, C.byref(pms), C.byref(bms)))
         ix = cls(h)
         ix.parse_ms, ix.build_ms = float(pms.value), float(bms.value)
         return ix

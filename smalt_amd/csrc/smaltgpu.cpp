@@ -10,6 +10,7 @@
 #include "smg_indexfile.hpp"
 #include "smg_indexbuild.h"
 #include "smg_fasta.hpp"
+#include "smg_fastq_ref.hpp"
 
 static thread_local std::string g_err;
 extern "C" const char *smaltgpu_last_error(void) { return g_err.c_str(); }
@@ -176,22 +177,36 @@ extern "C" int smaltgpu_index_build(smaltgpu_index **out, int device, const uint
 
 // ---- the same from the text of a FASTA file, parsed on the device (smg_fasta.hip) ----
 // bases in HBM (p->d_bases, the caller's), offsets, and the names cleaned on the host from the header lines the device found
-static int parse_fasta_text(int device, const char *text, uint64_t text_len, FastaParsed *p, std::vector<std::string> *names) {
+static int parse_fasta_text(int device, const char *text, uint64_t text_len, uint32_t flags, FastaParsed *p, std::vector<std::string> *names) {
   if (!text && text_len) return fail(SMALTGPU_EARG, "null argument");
+  if (flags & ~(uint32_t)SMALTGPU_TEXT_FASTQ) return fail(SMALTGPU_EARG, "unknown flags %#x", flags);
   HIPCHK(hipSetDevice(device));
-  char err[256] = "";
-  if (fasta_parse_device(text, text_len, fa_block_bytes(getenv("SMALTGPU_FASTA_BLOCK")), p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
+  char err[640] = "";
+  const uint32_t block = fa_block_bytes(getenv("SMALTGPU_FASTA_BLOCK"));
+  p->keep_fastq_text = (flags & SMALTGPU_TEXT_FASTQ) != 0;
+  uint64_t first = 0;
+  while (first < text_len && fa_isspace((uint8_t)text[first])) first++;
+  if (p->keep_fastq_text && first < text_len && (text[first] == '@' || text[first] == '+')) {
+    // the first prompt already says so: the FASTA route would refuse the text in its output pass, so it is not tried
+    if (fastq_ref_parse_device(text, text_len, block, nullptr, p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
+  } else if (fasta_parse_device(text, text_len, block, p, err, sizeof(err))) {
+    // a text with '@' or '+' prompts: the FASTA route has found that out and left the text in HBM; the records are walked instead
+    if (!p->d_text) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
+    uint8_t *d_text = p->d_text;
+    p->d_text = nullptr;
+    if (fastq_ref_parse_device(text, text_len, block, d_text, p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
+  }
   names->clear();
   for (const uint64_t o : p->hdr_text_off) names->push_back(fa_clean_name(text + o + 1, (size_t)(text_len - o - 1)));
   return SMALTGPU_OK;
 }
 
-extern "C" int smaltgpu_index_build_text(smaltgpu_index **out, int device, const char *text, uint64_t text_len, int32_t k, int32_t s, float *parse_ms,
-                                         float *build_ms) {
+extern "C" int smaltgpu_index_build_text_ex(smaltgpu_index **out, int device, const char *text, uint64_t text_len, int32_t k, int32_t s, float *parse_ms,
+                                            float *build_ms, uint32_t flags) {
   if (!out) return fail(SMALTGPU_EARG, "null argument");
   FastaParsed p;
   std::vector<std::string> names;
-  int rv = parse_fasta_text(device, text, text_len, &p, &names);
+  int rv = parse_fasta_text(device, text, text_len, flags, &p, &names);
   if (rv) return rv;
   std::vector<const char *> ptrs;
   for (const std::string &x : names) ptrs.push_back(x.c_str());
@@ -201,6 +216,11 @@ extern "C" int smaltgpu_index_build_text(smaltgpu_index **out, int device, const
   return rv;
 }
 
+extern "C" int smaltgpu_index_build_text(smaltgpu_index **out, int device, const char *text, uint64_t text_len, int32_t k, int32_t s, float *parse_ms,
+                                         float *build_ms) {
+  return smaltgpu_index_build_text_ex(out, device, text, text_len, k, s, parse_ms, build_ms, 0);
+}
+
 struct smaltgpu_fasta {
   std::vector<std::string> names;
   std::vector<const char *> name_ptrs;
@@ -208,11 +228,11 @@ struct smaltgpu_fasta {
   std::vector<uint8_t> bases;
 };
 
-extern "C" int smaltgpu_fasta_parse(smaltgpu_fasta **out, int device, const char *text, uint64_t text_len, smaltgpu_fasta_view *view) {
+extern "C" int smaltgpu_fasta_parse_ex(smaltgpu_fasta **out, int device, const char *text, uint64_t text_len, smaltgpu_fasta_view *view, uint32_t flags) {
   if (!out || !view) return fail(SMALTGPU_EARG, "null argument");
   FastaParsed p;
   smaltgpu_fasta *fa = new smaltgpu_fasta();
-  int rv = parse_fasta_text(device, text, text_len, &p, &fa->names);
+  int rv = parse_fasta_text(device, text, text_len, flags, &p, &fa->names);
   if (!rv) {
     fa->bases.resize((size_t)p.nbases + 1);
     if (p.nbases && hipMemcpy(fa->bases.data(), p.d_bases, p.nbases, hipMemcpyDeviceToHost) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "copy of the parsed sequences to the host failed");
@@ -227,6 +247,10 @@ extern "C" int smaltgpu_fasta_parse(smaltgpu_fasta **out, int device, const char
   view->parse_ms = p.pass_a_ms + p.compose_ms + p.pass_b_ms;
   *out = fa;
   return SMALTGPU_OK;
+}
+
+extern "C" int smaltgpu_fasta_parse(smaltgpu_fasta **out, int device, const char *text, uint64_t text_len, smaltgpu_fasta_view *view) {
+  return smaltgpu_fasta_parse_ex(out, device, text, text_len, view, 0);
 }
 
 extern "C" void smaltgpu_fasta_free(smaltgpu_fasta *fa) { delete fa; }

@@ -14,7 +14,8 @@
 // formats and writes the blocks in input order.
 //
 // `smaltgpu-map index` is `smalt index` (buildHashIndex, smalt.c:338-412): the text of the reference goes to the device whole,
-// smaltgpu_index_build_text parses it and builds the index there, smaltgpu_index_save writes the two files.
+// smaltgpu_index_build_text_ex parses it -- FASTA or FASTQ records, as the reference takes both -- and builds the index there,
+// smaltgpu_index_save writes the two files.
 //
 // `smaltgpu-map sample` is `smalt sample` (mapReads with MENU_SAMPLE, smalt.c:1395-1410): the pairs are counted in a pass of its
 // own, every n-th pair goes through the same stages, and the histogram of the insert sizes follows the SAM lines.
@@ -89,7 +90,8 @@ void usage() {
           "  of these pairs, the sampled and the smoothed histogram of their insert sizes and the section that -I reads\n"
           "\n"
           "usage: smaltgpu-map index [-k <int>] [-s <int>] [-g <device>] <index prefix> <reference.fa>[.gz]\n"
-          "  `smalt index`: word length <k> (default 13) sampled every <s> bases (default 6); reads the FASTA file, builds the index on the\n"
+          "  `smalt index`: word length <k> (default 13) sampled every <s> bases (default 6); reads the file in FASTA or FASTQ format\n"
+          "  (records of both kinds may be mixed; qualities are checked for their length and dropped), builds the index on the\n"
           "  device and writes <index prefix>.sma and <index prefix>.smi.  (The reference program takes <s> = <k> when -s is not given;\n"
           "  give both options to get the same index from both programs.)\n");
   exit(2);
@@ -226,7 +228,7 @@ int index_main(int argc, char **argv) {
   fprintf(stderr, "# Reading sequences ... %llu bytes of text (%.0f ms)\n", (unsigned long long)len, ms());
   smaltgpu_index *ix = nullptr;
   float parse_ms = 0, build_ms = 0;
-  if (smaltgpu_index_build_text(&ix, device, text, len, k, s, &parse_ms, &build_ms)) die("index", smaltgpu_last_error());
+  if (smaltgpu_index_build_text_ex(&ix, device, text, len, k, s, &parse_ms, &build_ms, SMALTGPU_TEXT_FASTQ)) die("index", smaltgpu_last_error());
   const char *const *names; const uint64_t *sop; int64_t nseq;
   if (smaltgpu_index_seqnames(ix, &names, &sop, &nseq)) die("index", smaltgpu_last_error());
   fprintf(stderr, "# %lld sequences, %llu bases; word length = %d bases, skip step = %d bases; device: parse %.2f ms, construction %.2f ms (%.0f ms)\n",

@@ -236,7 +236,11 @@ int fasta_parse_device(const char *text, uint64_t text_len, uint32_t block_bytes
   FA_HIP(hipEventElapsedTime(&out->compose_ms, ev[1], ev[2]));
   FA_HIP(hipEventElapsedTime(&out->pass_b_ms, ev[3], ev[4]));
   FA_HIP(hipMemcpy(&h_fq, d_fq, 8, hipMemcpyDeviceToHost));
-  if ((why = fa_refusal(text_len, h_end.state, h_end.hdr_off, h_fq))) { snprintf(err, errlen, "%s", why); goto fail; }
+  if ((why = fa_refusal(text_len, h_end.state, h_end.hdr_off, h_fq))) {
+    snprintf(err, errlen, "%s", why);
+    if (h_fq && out->keep_fastq_text) { out->d_text = d_text; d_text = nullptr; }        // for smg_fastq_ref.hip: the text stays in HBM
+    goto fail;
+  }
   hdr.resize((size_t)h_end.hdr_off);
   FA_HIP(hipMemcpy(hdr.data(), d_hdr, hdr.size() * sizeof(FaHeader), hipMemcpyDeviceToHost));
   out->seq_off.clear(); out->hdr_text_off.clear();

@@ -122,6 +122,10 @@ struct FastaParsed {
   uint64_t nbases = 0;
   std::vector<uint64_t> seq_off, hdr_text_off;
   float upload_ms = 0, pass_a_ms = 0, compose_ms = 0, pass_b_ms = 0;
+  // in: a text refused for its '@' / '+' prompts is left in HBM (d_text, padded to a multiple of FA_TILE; the caller's) for the
+  // reader of smg_fastq_ref.hpp
+  bool keep_fastq_text = false;
+  uint8_t *d_text = nullptr;
 };
 int fasta_parse_device(const char *text, uint64_t text_len, uint32_t block_bytes, FastaParsed *out, char *err, size_t errlen);
 
