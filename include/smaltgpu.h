@@ -142,7 +142,9 @@ void smaltgpu_params_default(smaltgpu_params *p, const smaltgpu_index *ix);
  * but ACGTU in either case counts as N); `seq_off`: nseq + 1 offsets into it (host memory); `names`: nseq strings.
  * _build takes host memory, _build_device bases already in HBM.  The image is built entirely on the device and is
  * ready for smaltgpu_mapper_create; smaltgpu_index_save writes <prefix>.sma / <prefix>.smi byte-compatible with the
- * reference's files.  build_ms (may be NULL) receives the device time of the construction. ---- */
+ * reference's files.  build_ms (may be NULL) receives the device time of the construction.  SMALTGPU_EARG for what the
+ * reference refuses: a sequence shorter than k, and with s > k a set of sequence lengths for which `smalt index` exits with
+ * "arguments outside expected range" (hashidx.c:494; the message names the sequence). ---- */
 int smaltgpu_index_build(smaltgpu_index **out, int device, const uint8_t *bases, const uint64_t *seq_off, const char *const *names,
                          int64_t nseq, int32_t k, int32_t s, float *build_ms);
 int smaltgpu_index_build_device(smaltgpu_index **out, int device, const uint8_t *d_bases, const uint64_t *seq_off, const char *const *names,

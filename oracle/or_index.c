@@ -92,14 +92,19 @@ static int cmp_rec(const void *a, const void *b)
 
 /* hashidx.c:465-531 (doWordsInSeq) restated: visit every sampled k-mer of one sequence.
  * `tuplectr` is the k-mer serial number (global base offset / s), `offs` the offset of the
- * first sampled k-mer within the sequence. */
+ * first sampled k-mer within the sequence.  Returns OR_ERR where the reference refuses the
+ * sequence (hashidx.c:494): with s > k a sequence can end so far in front of the next grid
+ * point that the offset carried over reaches s.  The reference keeps offset and countdown in
+ * an unsigned char; wherever this check passes the int arithmetic below gives the same values
+ * (s - ((d % s) & 255) and s - d % s agree modulo 256, and both are below 256). */
 typedef void (*kmer_fn)(void *ctx, uint64_t word, uint32_t serial);
-static void scan_kmers(const uint8_t *codes, uint32_t len, int k, int s, uint32_t *tuplectr,
+static int scan_kmers(const uint8_t *codes, uint32_t len, int k, int s, uint32_t *tuplectr,
                        int *offs, kmer_fn fn, void *ctx)
 {
   uint64_t word = 0;
   int countdown = k + *offs, bad = 0, o;
   uint32_t i;
+  if (*offs >= s) return OR_ERR;
   for (i = 0; i < len; i++) {
     if (codes[i] & 4) bad = k; else if (bad) bad--;
     word = (word << 2) + (codes[i] & 3);
@@ -112,6 +117,7 @@ static void scan_kmers(const uint8_t *codes, uint32_t len, int k, int s, uint32_
   if (o) o = s - o;
   *offs = o;
   *tuplectr += (uint32_t) ((k - countdown + o)/s);
+  return OR_OK;
 }
 
 typedef struct { const OrIndex *ix; KmerRec *rec; size_t n; uint32_t *cnt; int pass; } BuildCtx;
@@ -173,7 +179,9 @@ OrIndex *or_index_build(int nseq, const char *const *seqs, const uint32_t *lens,
     if (ctx.pass == 1) { ctx.rec = malloc((ctx.n + 1)*sizeof(KmerRec)); ctx.n = 0; }
     tuplectr = 0; offs = 0;
     for (i = 0; i < nseq; i++)
-      scan_kmers(codes + ix->sop[i], lens[i], k, s, &tuplectr, &offs, build_visit, &ctx);
+      if (scan_kmers(codes + ix->sop[i], lens[i], k, s, &tuplectr, &offs, build_visit, &ctx)) { /* hashidx.c:494 */
+        free(codes); free(ctx.rec); or_index_free(ix); return NULL;
+      }
   }
   free(codes);
   n = ctx.n;
@@ -240,7 +248,7 @@ OrIndex *or_index_build_fine(const OrIndex *main, int niv, const int64_t *sx, co
       if (sl < (uint32_t) k) continue;                                  /* hashidx.c:561-563 */
       if (sl + 1 > cap) { cap = sl + 1024; codes = realloc(codes, cap); }
       or_index_fetch(main, g, sl, codes);
-      scan_kmers(codes, sl, k, s, &tuplectr, &offs, build_visit, &ctx);
+      (void) scan_kmers(codes, sl, k, s, &tuplectr, &offs, build_visit, &ctx);   /* offs < s by construction */
     }
   }
   free(codes);

@@ -5,7 +5,8 @@
 // radix sort and two prefix sums over the sampled k-mers:
 //   * k-mer serial t covers the bases [t*s, t*s + k) of the concatenated reference; it is indexed iff it lies inside
 //     one sequence and holds no non-ACGT base (doWordsInSeq, hashidx.c:465-531: the sampling grid is global, serial
-//     numbers run on across sequence boundaries);
+//     numbers run on across sequence boundaries; with s > k the reference refuses some sets of sequence lengths and counts
+//     maxpos its own way -- index_carry of smg_indexbuild.h, run on the host in front of the kernels);
 //   * PERFECT: key = the 2k-bit word; pos lists = serials sorted by (key, serial); idx = prefix sums of key counts;
 //   * HASH32MIX (hashidx.c:155-172): key = hash32mix(word >> nbits_lo) % 2^(nbits_key - nbits_lo) << nbits_lo | low
 //     bits; serials sorted by (key, word_hi, serial); one (wordidx, posidx) entry per distinct (key, word_hi); idx =
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -78,10 +80,11 @@ __device__ inline uint32_t ib_hash32mix(uint32_t a) {        // hashidx.c:163-17
 }
 
 // one thread per k-mer serial.  K32 (PERFECT with 2k <= 30): 32-bit sort key, the sentinel 2^2k for serials that are not
-// indexed (they sort behind every key), value = serial; the number of indexed serials goes to *nvalid.  Otherwise:
-// validity flag and 64-bit sort key ((key << 32) | word_hi; PERFECT: the word) for the compaction path.
+// indexed (they sort behind every key), value = serial; the number of indexed serials goes to *nvalid.  Otherwise (HASH32MIX; a
+// PERFECT index with 2k > 30 would be k = 16, which build_index_device refuses): validity flag and 64-bit sort key
+// ((key << 32) | word_hi) for the compaction path.
 template <bool K32>
-__global__ void __launch_bounds__(256) k_ib_kmers(const uint8_t *ascii, const uint64_t *sop, int nseq, uint64_t ntup, int k, int s, int typ,
+__global__ void __launch_bounds__(256) k_ib_kmers(const uint8_t *ascii, const uint64_t *sop, int nseq, uint64_t ntup, int k, int s,
                                                   int nbits_key, int nbits_lo, uint32_t *flag, uint64_t *key64, uint32_t *key32, uint32_t *pos32,
                                                   unsigned long long *nvalid) {
   unsigned long long mine = 0;
@@ -116,14 +119,11 @@ __global__ void __launch_bounds__(256) k_ib_kmers(const uint8_t *ascii, const ui
     } else {
       uint64_t kv = 0;
       if (ok) {
-        if (typ == IDX_PERFECT) kv = word;
-        else {
-          const uint64_t mask_lo = (1ull << nbits_lo) - 1ull;
-          const uint32_t whi = (uint32_t)(word >> nbits_lo);
-          const uint32_t keymod = 1u << (nbits_key - nbits_lo);
-          const uint32_t key = ((ib_hash32mix(whi) % keymod) << nbits_lo) + (uint32_t)(word & mask_lo);
-          kv = ((uint64_t)key << 32) | whi;
-        }
+        const uint64_t mask_lo = (1ull << nbits_lo) - 1ull;
+        const uint32_t whi = (uint32_t)(word >> nbits_lo);
+        const uint32_t keymod = 1u << (nbits_key - nbits_lo);
+        const uint32_t key = ((ib_hash32mix(whi) % keymod) << nbits_lo) + (uint32_t)(word & mask_lo);
+        kv = ((uint64_t)key << 32) | whi;
       }
       flag[t] = ok ? 1u : 0u;
       key64[t] = kv;
@@ -146,10 +146,6 @@ __global__ void __launch_bounds__(256) k_ib_runend32(const uint32_t *skey, uint6
   for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a < n; a += (uint64_t)gridDim.x * 256)
     if (a + 1 == n || skey[a] != skey[a + 1]) idx[(uint64_t)skey[a] + 1] = (uint32_t)(a + 1);
 }
-__global__ void __launch_bounds__(256) k_ib_runend64(const uint64_t *skey, uint64_t n, uint32_t *idx) {
-  for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a < n; a += (uint64_t)gridDim.x * 256)
-    if (a + 1 == n || skey[a] != skey[a + 1]) idx[skey[a] + 1] = (uint32_t)(a + 1);
-}
 
 // HASH32MIX: heads of runs of equal (key, word_hi)
 __global__ void __launch_bounds__(256) k_ib_heads(const uint64_t *skey, uint64_t n, uint32_t *head) {
@@ -163,7 +159,17 @@ __global__ void __launch_bounds__(256) k_ib_words(const uint64_t *skey, const ui
   }
 }
 
-static inline unsigned ib_grid(uint64_t n) { uint64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g)); }
+static inline unsigned ib_grid(uint64_t n, unsigned cap) { uint64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g)); }
+
+// SMALTGPU_INDEX_GRID=<1..65536> caps the workgroups of every launch of the construction.  It exists for the tests only: with
+// the default of 65536 a kernel's grid-stride loop runs a second time only past 16.7 M serials or words, with a cap of 1 or 3
+// it does so on a reference of a few kB.  Anything else is ignored.
+static unsigned ib_grid_cap(const char *v) {
+  if (!v || !*v) return 65536;
+  char *end = nullptr;
+  const long x = strtol(v, &end, 10);
+  return (*end || x < 1 || x > 65536) ? 65536u : (unsigned)x;
+}
 
 // selectHashTyp (smalt.c:268-332)
 int index_geometry(int k, int s, uint64_t totlen, int *typ, int *nbits_key, int *nbits_lo) {
@@ -199,13 +205,21 @@ int build_index_device(const uint8_t *d_ascii, uint64_t tot, const uint64_t *h_s
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (index_geometry(k, s, tot, &b.typ, &b.nbits_key, &b.nbits_lo) || b.nbits_key > 31 || nseq < 1 || s > 200) { snprintf(err, errlen, "unsupported index geometry (k=%d s=%d)", k, s); return -1; }
   for (int i = 0; i < nseq; i++) if (h_sop[i + 1] - h_sop[i] < (uint64_t)k) { snprintf(err, errlen, "sequence %d is shorter than the word length (hashidx.c:499)", i); return -1; }
+  {                                                                        // the reference's walk over the lengths: refusal and maxpos (only s > k leaves the grid)
+    const int64_t bad = index_carry(h_sop, nseq, k, s, &b.maxpos);         // hashidx.c:992
+    if (bad >= 0) {
+      snprintf(err, errlen, "the reference refuses sampling step %d with word length %d for sequence %lld: the one in front of it ends too far before the next sampled word (hashidx.c:494)",
+               s, k, (long long)bad);
+      return -1;
+    }
+  }
   {
+  const unsigned cap = ib_grid_cap(getenv("SMALTGPU_INDEX_GRID"));      // read once per build
   b.nkeys = 1u << b.nbits_key;
   const uint64_t ntup = (tot + (uint64_t)s - 1) / (uint64_t)s;           // serials 0 .. ntup-1 start inside the reference
   const uint64_t nwords = tot / 10 + 1;
   const bool k32 = b.typ == IDX_PERFECT && 2 * k <= 30;                  // 32-bit keys with a sentinel behind the largest word
 #define IB_TMP(call_null, call_real) { IB_HIP(call_null); if (need > tmp_bytes) { if (tmp) IB_HIP(hipFree(tmp)); tmp = nullptr; tmp_bytes = need; IB_HIP(hipMalloc(&tmp, tmp_bytes)); } IB_HIP(call_real); }
-  b.maxpos = ntup > 0 ? (uint32_t)(ntup - 1) : 0;                        // hashidx.c:992
   IB_HIP(hipEventCreate(&e0)); IB_HIP(hipEventCreate(&e1));
   IB_HIP(hipMalloc((void **)&d_sop, ((size_t)nseq + 1) * 8));
   IB_HIP(hipMemcpy(d_sop, h_sop, ((size_t)nseq + 1) * 8, hipMemcpyHostToDevice));
@@ -225,9 +239,9 @@ int build_index_device(const uint8_t *d_ascii, uint64_t tot, const uint64_t *h_s
   IB_HIP(hipEventRecord(e0, 0));
   IB_HIP(hipMemsetAsync(d_nvalid, 0, 8, 0));
   IB_HIP(hipMemsetAsync(b.idx, 0, ((size_t)b.nkeys + 2) * 4, 0));
-  hipLaunchKernelGGL(k_ib_pack, dim3(ib_grid(nwords)), dim3(256), 0, 0, d_ascii, tot, nwords, b.packed);
+  hipLaunchKernelGGL(k_ib_pack, dim3(ib_grid(nwords, cap)), dim3(256), 0, 0, d_ascii, tot, nwords, b.packed);
   if (k32) {
-    hipLaunchKernelGGL(k_ib_kmers<true>, dim3(ib_grid(ntup)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, d_sop, nseq, ntup, k, s, b.typ, b.nbits_key, b.nbits_lo,
+    hipLaunchKernelGGL(k_ib_kmers<true>, dim3(ib_grid(ntup, cap)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, d_sop, nseq, ntup, k, s, b.nbits_key, b.nbits_lo,
                        (uint32_t *)nullptr, (uint64_t *)nullptr, key32, opos, d_nvalid);
     IB_HIP(hipGetLastError());
     // stable sort by key: serials of equal keys stay ascending, serials that are not indexed end up behind
@@ -236,10 +250,10 @@ int build_index_device(const uint8_t *d_ascii, uint64_t tot, const uint64_t *h_s
     IB_HIP(hipMemcpy(&h_nvalid, d_nvalid, 8, hipMemcpyDeviceToHost));
     n = h_nvalid;
     b.npos = (uint32_t)n;
-    hipLaunchKernelGGL(k_ib_runend32, dim3(ib_grid(n)), dim3(256), 0, 0, skey32, n, b.idx);
+    hipLaunchKernelGGL(k_ib_runend32, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey32, n, b.idx);
     IB_HIP(hipGetLastError());
   } else {
-    hipLaunchKernelGGL(k_ib_kmers<false>, dim3(ib_grid(ntup)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, d_sop, nseq, ntup, k, s, b.typ, b.nbits_key, b.nbits_lo,
+    hipLaunchKernelGGL(k_ib_kmers<false>, dim3(ib_grid(ntup, cap)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, d_sop, nseq, ntup, k, s, b.nbits_key, b.nbits_lo,
                        flag, key64, (uint32_t *)nullptr, (uint32_t *)nullptr, d_nvalid);
     IB_HIP(hipGetLastError());
     // ordered compaction of the indexed serials
@@ -255,20 +269,17 @@ int build_index_device(const uint8_t *d_ascii, uint64_t tot, const uint64_t *h_s
     IB_HIP(hipMalloc((void **)&skey, (n + 2) * 8));
     IB_HIP(hipMalloc((void **)&opos, (n + 1) * 4));
     IB_HIP(hipMalloc((void **)&b.pos, (n + 1) * 4));
-    hipLaunchKernelGGL(k_ib_scatter, dim3(ib_grid(ntup)), dim3(256), 0, 0, flag, slot, key64, ntup, okey, opos);
+    hipLaunchKernelGGL(k_ib_scatter, dim3(ib_grid(ntup, cap)), dim3(256), 0, 0, flag, slot, key64, ntup, okey, opos);
     IB_HIP(hipGetLastError());
     {
-      const unsigned end_bit = b.typ == IDX_PERFECT ? (unsigned)(2 * k) : (unsigned)(32 + b.nbits_key);
+      const unsigned end_bit = (unsigned)(32 + b.nbits_key);
       IB_TMP(rocprim::radix_sort_pairs(nullptr, need, okey, skey, opos, b.pos, (size_t)n, 0u, end_bit, 0),
              rocprim::radix_sort_pairs(tmp, need, okey, skey, opos, b.pos, (size_t)n, 0u, end_bit, 0));
     }
-    if (b.typ == IDX_PERFECT) {
-      hipLaunchKernelGGL(k_ib_runend64, dim3(ib_grid(n)), dim3(256), 0, 0, skey, n, b.idx);
-      IB_HIP(hipGetLastError());
-    } else {
+    {
       uint32_t lh = 0, ls = 0;
       IB_HIP(hipMalloc((void **)&head, (n + 1) * 4));
-      hipLaunchKernelGGL(k_ib_heads, dim3(ib_grid(n)), dim3(256), 0, 0, skey, n, head);
+      hipLaunchKernelGGL(k_ib_heads, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey, n, head);
       IB_HIP(hipGetLastError());
       IB_TMP(rocprim::exclusive_scan(nullptr, need, head, slot, 0u, (size_t)n, rocprim::plus<uint32_t>(), 0),
              rocprim::exclusive_scan(tmp, need, head, slot, 0u, (size_t)n, rocprim::plus<uint32_t>(), 0));
@@ -281,7 +292,7 @@ int build_index_device(const uint8_t *d_ascii, uint64_t tot, const uint64_t *h_s
       IB_HIP(hipMalloc((void **)&b.posidx, ((size_t)b.nwords + 2) * 4));
       IB_HIP(hipMemsetAsync(b.wordidx, 0, ((size_t)b.nwords + 2) * 4, 0));
       IB_HIP(hipMemsetAsync(b.posidx, 0, ((size_t)b.nwords + 2) * 4, 0));
-      hipLaunchKernelGGL(k_ib_words, dim3(ib_grid(n)), dim3(256), 0, 0, skey, head, slot, n, b.wordidx, b.posidx, b.idx);
+      hipLaunchKernelGGL(k_ib_words, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey, head, slot, n, b.wordidx, b.posidx, b.idx);
       IB_HIP(hipGetLastError());
       IB_HIP(hipMemcpyAsync(b.posidx + b.nwords, &b.npos, 4, hipMemcpyHostToDevice, 0));       // posidx[nwords] = npos
     }

@@ -89,10 +89,14 @@ def test_mapping_through_a_built_image_equals_mapping_through_its_files(oracle_b
 
 
 def test_index_build_rejects_what_the_reference_rejects():
-    """A sequence shorter than the word length (hashidx.c:499) and word lengths the index types do not cover."""
+    """A sequence shorter than the word length (hashidx.c:499), word lengths the index types do not cover, and a sampling step above the
+    word length behind a sequence that ends too far in front of the next grid point (hashidx.c:494; tests/test_gpu_index_shapes.py)."""
     from smalt_amd import api
     with pytest.raises(api.SmaltGpuError):
         api.Index.build([b"ACGTACGTACGTACGTACGTACGT" * 50, b"ACGTACG"], ["a", "b"], 13, 6, 0)
+    with pytest.raises(api.SmaltGpuError) as ei:                 # k = 8, s = 13: 8 bases, then the next grid point is 5 bases on
+        api.Index.build([b"ACGTACGT", b"ACGTACGTACGTACGTACGTACGT" * 50], ["a", "b"], 8, 13, 0)
+    assert "the reference refuses" in str(ei.value) and "sequence 1:" in str(ei.value)
     with pytest.raises(api.SmaltGpuError):
         api.Index.build([b"ACGT" * 5000], ["a"], 22, 6, 0)
     ix = api.Index.build([b"ACGT" * 5000], ["a"], 13, 6, 0)       # and a loaded handle cannot be saved, only a built one
