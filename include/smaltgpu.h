@@ -737,7 +737,8 @@ int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint
 /* O1 and the K3 driver on their own (kernels k_replay and k_align): the reads are uploaded and encoded, the caller's ranked
  * candidates WITH their first-pass scores take the place of what the candidate stage and the score kernels leave in the batch,
  * and the tail of a mapping call runs on the mapper's own scratch, slots and capacities: k_replay, then both passes of k_align.
- * The production score kernels are not part of it (their task routing follows lists the candidate stage builds), nor are the
+ * The production score kernels are not part of it (their task routing follows lists the candidate stage builds; smaltgpu_score_pool
+ * below shows what they left after a mapping call), nor are the
  * complexity-weighted scores (SMALTGPU_EARG with SMALTGPU_FLG_CMPLXW).  Read r owns cands[cand_off[r] .. cand_off[r + 1]) in rank
  * order and cover_deficit[2 r + strand].  Of ctx (may be NULL) prev_max, min_swatscor and raw_alignments are honoured;
  * SMALTGPU_EARG if iv_off, fine_index or seed_range is set.  flags: SMALTGPU_ALIGN_CANDS_ANTIDIAG or 0.
@@ -772,6 +773,37 @@ typedef struct smaltgpu_align_cands_out {
 int smaltgpu_align_cands_batch(smaltgpu_mapper *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *read_off, uint32_t nreads,
                                const smaltgpu_params *par, const smaltgpu_callctx *ctx, const uint64_t *cand_off, const smaltgpu_cand *cands,
                                const uint32_t *cover_deficit, uint32_t flags, smaltgpu_align_cands_out *out);
+
+/* What the first-pass score stage (the launchers of K2a and K2b in a mapping call) left in the candidate pool of the mapper's
+ * last mapping call, debug or not: the stream is waited for and the first min(rc_count, rccap) records come back in pool order
+ * -- the records of a read are contiguous and in rank order, the reads in the order their waves reserved room -- in a host copy
+ * the mapper owns until its next call.  Nothing is launched and nothing on the device changes.  With them the geometry the task
+ * routing of the stage depends on (tests/score_route_ref.py restates the routing).  After a call that re-mapped reads of an
+ * overflowing batch the pool is that of the last of the smaller batches. */
+enum { SMALTGPU_RCF_REVERSE = 1, SMALTGPU_RCF_SCORED = 2, SMALTGPU_RCF_BANDED = 4 /* K2b scores it: by S7's rule, or after a K2a score >= 65535 */,
+       SMALTGPU_RCF_ERR = 8, SMALTGPU_RCF_QN = 16 /* the read holds a non-ACGT code */, SMALTGPU_RCF_BSCORED = 32 /* swscor is the wave kernel's K2b score */ };
+typedef struct smaltgpu_pool_rec {
+  uint64_t rs, re;                   /* window in sequence sqidx (sqidx < 0: in the concatenated set), 0-based inclusive */
+  uint32_t qs, qe;
+  int32_t band_l, band_r;
+  int32_t sqidx;
+  uint32_t flags;                    /* SMALTGPU_RCF_*, as the stage left them */
+  uint32_t cover;
+  int32_t swscor;
+  uint32_t rid;                      /* read of the batch */
+  uint32_t pad;
+} smaltgpu_pool_rec;
+typedef struct smaltgpu_score_pool_out {
+  const smaltgpu_pool_rec *rec;      /* [nrec] */
+  uint32_t nrec;                     /* min(rc_count, rccap) */
+  uint32_t rc_count;                 /* records the batch asked for (above rccap: the pool overflowed) */
+  uint32_t rccap, long_cap, strip_cap;   /* capacities of the pool, of the list of windows above 248 bases and of the strip list */
+  uint32_t tile_qmax;                /* longest read of the register-tiled kernels: tile_g * tile_c, 0 where the mapper has no tiling */
+  uint32_t wincap;                   /* longest window of the strip kernels and of the wave form of K2b */
+  uint32_t tile_g, tile_c;
+  uint32_t full_grid, strip_grid;    /* workgroups of the register-tiled and of the strip kernels */
+} smaltgpu_score_pool_out;
+int smaltgpu_score_pool(smaltgpu_mapper *m, smaltgpu_score_pool_out *out);
 
 const char *smaltgpu_last_error(void);
 int smaltgpu_device_count(void);

@@ -157,6 +157,18 @@ class AlignCandsOut(C.Structure):      # smaltgpu_align_cands_out
     _fields_ = [("batch", BatchOut), ("ctl", C.POINTER(ReadCtl)), ("n_deferred", C.c_uint32)]
 
 
+class PoolRec(C.Structure):            # smaltgpu_pool_rec
+    _fields_ = [("rs", C.c_uint64), ("re", C.c_uint64), ("qs", C.c_uint32), ("qe", C.c_uint32), ("band_l", C.c_int32), ("band_r", C.c_int32),
+                ("sqidx", C.c_int32), ("flags", C.c_uint32), ("cover", C.c_uint32), ("swscor", C.c_int32), ("rid", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ScorePoolOut(C.Structure):       # smaltgpu_score_pool_out
+    _fields_ = [("rec", C.POINTER(PoolRec)), ("nrec", C.c_uint32), ("rc_count", C.c_uint32), ("rccap", C.c_uint32), ("long_cap", C.c_uint32),
+                ("strip_cap", C.c_uint32), ("tile_qmax", C.c_uint32), ("wincap", C.c_uint32), ("tile_g", C.c_uint32), ("tile_c", C.c_uint32),
+                ("full_grid", C.c_uint32), ("strip_grid", C.c_uint32)]
+
+
+RCF_REVERSE, RCF_SCORED, RCF_BANDED, RCF_ERR, RCF_QN, RCF_BSCORED = 1, 2, 4, 8, 16, 32      # SMALTGPU_RCF_*
 CAND_REVERSE, CAND_ERR = 1, 2                                  # SMALTGPU_CAND_*
 ALIGN_CANDS_ANTIDIAG = 0x100                                   # SMALTGPU_ALIGN_CANDS_ANTIDIAG
 HITRUN_NONE, HITRUN_SORTED, HITRUN_OVERFLOW = 0, 1, 2         # SMALTGPU_HITRUN_*
@@ -286,6 +298,7 @@ def lib():
                                                  C.POINTER(C.c_uint64), C.POINTER(Cand), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(AlignCandsOut)]
         L.smaltgpu_fine_index_batch.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(Interval), C.c_uint32, C.c_uint32, C.POINTER(FineOut)]
         L.smaltgpu_cands_geometry.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.smaltgpu_score_pool.argtypes = [C.c_void_p, C.POINTER(ScorePoolOut)]
         L.smaltgpu_sort_u64_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.smaltgpu_sample_interval.argtypes = [C.c_uint64, C.c_int]
         L.smaltgpu_inshist_from_sample.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_uint64]
@@ -926,6 +939,23 @@ class Mapper:
         g = (C.c_uint32 * 8)()
         _check(lib().smaltgpu_cands_geometry(self.h, g))
         return dict(hcap_strand=g[0], candcap=g[1], lds_bytes=g[2], hcap_strand2=g[3], candcap2=g[4], lds_bytes2=g[5], qmax=g[6], iv_max=g[7])
+
+    def score_pool(self):
+        """The candidate pool as the first-pass score stage of the last mapping call left it (smaltgpu_score_pool) -> (records,
+        geometry): a numpy structured array of the first min(rc_count, rccap) records in pool order (fields rs, re, qs, qe, band_l,
+        band_r, sqidx, flags, cover, swscor, rid; flags are RCF_*) and a dict of rc_count, rccap, long_cap, strip_cap, tile_qmax,
+        wincap, tile_g, tile_c, full_grid, strip_grid."""
+        import numpy as np
+        out = ScorePoolOut()
+        _check(lib().smaltgpu_score_pool(self.h, C.byref(out)))
+        dt = np.dtype([("rs", np.uint64), ("re", np.uint64), ("qs", np.uint32), ("qe", np.uint32), ("band_l", np.int32), ("band_r", np.int32),
+                       ("sqidx", np.int32), ("flags", np.uint32), ("cover", np.uint32), ("swscor", np.int32), ("rid", np.uint32), ("pad", np.uint32)])
+        assert dt.itemsize == C.sizeof(PoolRec)
+        n = int(out.nrec)
+        rec = np.frombuffer(C.string_at(out.rec, n * dt.itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+        geo = {k: int(getattr(out, k)) for k in ("rc_count", "rccap", "long_cap", "strip_cap", "tile_qmax", "wincap", "tile_g", "tile_c",
+                                                 "full_grid", "strip_grid")}
+        return rec, geo
 
     def sort_u64_batch(self, arrays, form: int):
         """Stand-alone 64-bit key sorts (smaltgpu_sort_u64_batch): list of uint64 numpy arrays -> list of sorted arrays.

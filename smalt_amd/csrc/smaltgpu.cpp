@@ -544,7 +544,7 @@ extern "C" int smaltgpu_mapper_create_ex(smaltgpu_mapper **out, const smaltgpu_i
   {
     m->wincap = 4 * m->qmax + 1024;
     m->strip_grid = 5120;                              // workgroups (one wave each) of the strip kernels: five per SIMD (96 registers); 2048: 5.2, 4096: 6.0, 5120: 6.2 TCUPS at 8 kbp
-    if (const char *e = getenv("SMALTGPU_STRIP_GRID")) { const long v = atol(e); if (v >= 64 && v <= 16384) m->strip_grid = (uint32_t)v; }   // tuning hook
+    if (const char *e = getenv("SMALTGPU_STRIP_GRID")) { const long v = atol(e); if (v >= 1 && v <= 16384) m->strip_grid = (uint32_t)v; }   // tuning hook; a few workgroups: more tasks than workgroups on a small batch (tests/test_gpu_score_route.py)
     // tuning hook; with a few workgroups a wave meets the same read in successive iterations even on a small batch (tests/test_gpu_sw_prologue.py)
     if (const char *e = getenv("SMALTGPU_SWFULL_GRID")) { const long v = atol(e); if (v >= 1 && v <= 16384) m->full_grid = (uint32_t)v; }
     if ((uint64_t)m->strip_grid * m->wincap * 18 > (8ull << 30)) m->strip_grid = (uint32_t)((8ull << 30) / ((uint64_t)m->wincap * 18));

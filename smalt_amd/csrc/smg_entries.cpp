@@ -324,6 +324,30 @@ extern "C" int smaltgpu_cands_geometry(smaltgpu_mapper *m, uint32_t out[8]) {
   return SMALTGPU_OK;
 }
 
+// The candidate pool as the score stage of the last mapping call left it, and the geometry its task routing follows (read-only)
+static_assert(sizeof(smaltgpu_pool_rec) == sizeof(RCand) && offsetof(smaltgpu_pool_rec, flags) == offsetof(RCand, flags) &&
+              offsetof(smaltgpu_pool_rec, swscor) == offsetof(RCand, swscor) && offsetof(smaltgpu_pool_rec, rid) == offsetof(RCand, rid),
+              "smaltgpu_pool_rec is the layout of RCand");
+static_assert(SMALTGPU_RCF_REVERSE == RCF_REVERSE && SMALTGPU_RCF_SCORED == RCF_SCORED && SMALTGPU_RCF_BANDED == RCF_BANDED &&
+              SMALTGPU_RCF_ERR == RCF_ERR && SMALTGPU_RCF_QN == RCF_QN && SMALTGPU_RCF_BSCORED == RCF_BSCORED, "SMALTGPU_RCF_* mirror RCF_*");
+extern "C" int smaltgpu_score_pool(smaltgpu_mapper *m, smaltgpu_score_pool_out *out) {
+  if (!m || !out) return fail(SMALTGPU_EARG, "null argument");
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  const Batch &b = m->b;
+  uint32_t count = 0;
+  HIPCHK(hipMemcpy(&count, b.rc_count, sizeof(count), hipMemcpyDeviceToHost));
+  const uint32_t n = count < b.rccap ? count : b.rccap;
+  if (fetch(m->h_pool, b.rcpool, n)) return SMALTGPU_ENODEV;
+  int G = 0, C = 0;
+  (void)sw_full_geometry(m->max_len, &G, &C);
+  memset(out, 0, sizeof(*out));
+  out->rec = (const smaltgpu_pool_rec *)m->h_pool.data(); out->nrec = n; out->rc_count = count;
+  out->rccap = b.rccap; out->long_cap = b.long_cap; out->strip_cap = b.strip_cap; out->tile_qmax = b.tile_qmax; out->wincap = m->wincap;
+  out->tile_g = (uint32_t)G; out->tile_c = (uint32_t)C; out->full_grid = m->full_grid; out->strip_grid = m->strip_grid;
+  return SMALTGPU_OK;
+}
+
 extern "C" int smaltgpu_sort_u64_batch(smaltgpu_mapper *m, const uint64_t *keys, const uint32_t *off, uint32_t narr, int form, uint64_t *out) {
   if (!m || !keys || !off || !out) return fail(SMALTGPU_EARG, "null argument");
   if (form < 0 || form > 5) return fail(SMALTGPU_EARG, "unknown form %d", form);

@@ -157,6 +157,7 @@ struct smaltgpu_mapper {
   struct HitsHost { std::vector<HitInfoHdr> hi; std::vector<uint32_t> n_seeds, seed_rank, status; std::vector<SeedRec> seeds; std::vector<uint8_t> qmask;
                     std::vector<HitRun> runs; std::vector<uint64_t> pool; } hh;
   std::vector<ReadCtl> h_ctl;               // what k_replay left behind (smaltgpu_align_cands_batch, test entry)
+  std::vector<RCand> h_pool;                // the candidate pool behind the score stage (smaltgpu_score_pool, test entry)
   hipEvent_t ev[T_NUM + 1] = {nullptr};
   double ms[T_NUM] = {0};
   unsigned long long work[WK_NWORK] = {0};

@@ -183,6 +183,13 @@ class Mapper:
         scored = [dict(swscor=cp[i].swscor, used_simd=cp[i].used_simd) for i in range(ns.value)]
         return rv, self._results(), scored
 
+    def cands(self):
+        """or_map_cands: the candidates the last read's score pass went through, in rank order (without FLG_BEST: all ranked ones)"""
+        ns = C.c_int()
+        cp = lib().or_map_cands(self.m, C.byref(ns))
+        return [dict(reverse=int(cp[i].flags & 1), qs=cp[i].qs, qe=cp[i].qe, rs=cp[i].rs, re=cp[i].re, band_l=cp[i].band_l, band_r=cp[i].band_r,
+                     sqidx=int(cp[i].sqidx), cover=cp[i].cover, swscor=cp[i].swscor, used_simd=cp[i].used_simd) for i in range(ns.value)]
+
     def thresholds(self):
         """(bandwidth_min, min_swatscor, scorlen_min, go) of the last read's threshold block"""
         a = (C.c_int * 4)()

@@ -16,6 +16,7 @@ def test_library_exports_declared_symbols():
     assert "smaltgpu_hits_batch" in declared and "smaltgpu_sort_u64_batch" in declared
     assert "smaltgpu_seed_batch" in declared and "smaltgpu_gather_batch" in declared and "smaltgpu_rank_sort_batch" in declared
     assert "smaltgpu_align_cands_batch" in declared
+    assert "smaltgpu_score_pool" in declared
     lib = ctypes.CDLL(os.path.join(ROOT, "smalt_amd", "libsmaltgpu.so"))
     for name in declared:
         assert hasattr(lib, name), name
