@@ -212,6 +212,9 @@ void smaltgpu_mapper_free(smaltgpu_mapper *m);
 /* host threads a mapper may use for its own host work (the copy of a batch's results into read order in smaltgpu_fetch_end);
  * default 1 -- the reference's worker owns one thread (threads.c).  smaltgpu_map_pairs sets it from pair_opts.nthreads. */
 int smaltgpu_mapper_set_host_threads(smaltgpu_mapper *m, int nthreads);
+/* diagnostic, read only: device batches the mapper has run so far to map reads again that did not fit a work pool (the recovery of
+ * smaltgpu_map_batch, smaltgpu_map_batch_ctx and smaltgpu_map_batch_ctx_resident from SMALTGPU_ECAP); 0 = no call ever overflowed */
+int smaltgpu_mapper_remap_batches(const smaltgpu_mapper *m, uint64_t *nbatches);
 
 /* Map a block of reads (the unit processArgBlock smalt.c:1221 hands to a worker).  `bases`:
  * concatenated ASCII reads, `quals`: concatenated phred+33 or NULL, `read_off`: nreads+1
@@ -329,7 +332,12 @@ int smaltgpu_mapper_capacity(const smaltgpu_mapper *m, uint32_t *max_batch_reads
 
 /* Same with the inputs already resident in HBM (device pointers); results stay on the device
  * until smaltgpu_fetch_results().  Used by bench.py so that the timed region starts with the
- * reads in HBM. */
+ * reads in HBM.  The offsets live on the device, so the library cannot check them and the caller
+ * guarantees what the kernels rely on: d_read_off[0] is 0 (d_bases / d_quals point at the first
+ * read of the batch and may have any alignment), the offsets do not decrease, no read is longer
+ * than the mapper's max_read_len, and total_bases equals d_read_off[nreads].  A batch that
+ * overflows a work pool is NOT mapped again here: the reads that did not fit keep SMALTGPU_ECAP
+ * in stat[].errcode, without results, and the fetch call returns that code with `out` filled. */
 int smaltgpu_map_batch_device(smaltgpu_mapper *m, const uint8_t *d_bases, const uint8_t *d_quals,
                               const uint64_t *d_read_off, uint32_t nreads, uint64_t total_bases,
                               const smaltgpu_params *par);

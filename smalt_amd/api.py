@@ -270,6 +270,13 @@ def lib():
         L.smaltgpu_index_seqnames.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int64)]
         L.smaltgpu_map_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                                                 C.POINTER(Params)]
+        L.smaltgpu_map_batch_ctx_resident.argtypes = [C.c_void_p, C.POINTER(ResidentReads), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Params),
+                                                      C.POINTER(CallCtx), C.POINTER(BatchOut)]
+        L.smaltgpu_hit_totals_resident.argtypes = [C.c_void_p, C.POINTER(ResidentReads), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Params), C.POINTER(C.c_uint32)]
+        L.smaltgpu_mapper_set_host_threads.argtypes = [C.c_void_p, C.c_int]
+        L.smaltgpu_mapper_remap_batches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.smaltgpu_fetch_begin.argtypes = [C.c_void_p]
+        L.smaltgpu_fetch_end.argtypes = [C.c_void_p, C.POINTER(BatchOut)]
         L.smaltgpu_fetch_results.argtypes = [C.c_void_p, C.POINTER(BatchOut)]
         L.smaltgpu_synchronize.argtypes = [C.c_void_p]
         L.smaltgpu_timers.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
@@ -599,15 +606,9 @@ class Mapper:
             _check(rv)
         return self._unpack(out)
 
-    def map_batch_ctx(self, reads: Sequence[bytes], quals: Optional[Sequence[bytes]], params: Params, intervals=None, min_swatscor=None,
-                      prev_max=None, fine_index: bool = False, raw_alignments: bool = False, seed_range=None, allow_read_errors: bool = False):
-        """One round of rmapPair over a batch (smaltgpu_map_batch_ctx): intervals = per read a list of (sidx, lo, hi) or None
-        for no restriction at all; min_swatscor = per-read thresholds; prev_max = per read (max, 2ndmax) of the ResultSet
-        the call appends to; fine_index = seed against the on-the-fly k=5 index of the intervals; seed_range = per read the
-        (first, last) base its k-mer words come from (the second call of a split read); allow_read_errors as in map_batch.
-        -> (results, stats, cand_first flags per result)"""
-        bases, q, off = self._pack(reads, quals)
-        n = len(reads)
+    @staticmethod
+    def _ctx(n, intervals, min_swatscor, prev_max, fine_index, raw_alignments, seed_range):
+        """the smaltgpu_callctx of a round over n reads -> (CallCtx, the arrays it points to: keep them until the call returns)"""
         ctx = CallCtx()
         keep = []
         if intervals is not None:
@@ -635,6 +636,18 @@ class Mapper:
             keep.append(sr)
         ctx.fine_index = 1 if fine_index else 0
         ctx.raw_alignments = 1 if raw_alignments else 0
+        return ctx, keep
+
+    def map_batch_ctx(self, reads: Sequence[bytes], quals: Optional[Sequence[bytes]], params: Params, intervals=None, min_swatscor=None,
+                      prev_max=None, fine_index: bool = False, raw_alignments: bool = False, seed_range=None, allow_read_errors: bool = False):
+        """One round of rmapPair over a batch (smaltgpu_map_batch_ctx): intervals = per read a list of (sidx, lo, hi) or None
+        for no restriction at all; min_swatscor = per-read thresholds; prev_max = per read (max, 2ndmax) of the ResultSet
+        the call appends to; fine_index = seed against the on-the-fly k=5 index of the intervals; seed_range = per read the
+        (first, last) base its k-mer words come from (the second call of a split read); allow_read_errors as in map_batch.
+        -> (results, stats, cand_first flags per result)"""
+        bases, q, off = self._pack(reads, quals)
+        n = len(reads)
+        ctx, keep = self._ctx(n, intervals, min_swatscor, prev_max, fine_index, raw_alignments, seed_range)
         out = BatchOut()
         rv = lib().smaltgpu_map_batch_ctx(self.h, bases, q, off, n, C.byref(params), C.byref(ctx), C.byref(out))
         if rv != 0 and not (allow_read_errors and rv in (ECAP, EINTERNAL, ESCORE, ECPLX) and out.nreads == n):
@@ -649,6 +662,61 @@ class Mapper:
         out = (C.c_uint32 * max(1, len(reads)))()
         _check(lib().smaltgpu_hit_totals(self.h, bases, q, off, len(reads), C.byref(params), out))
         return list(out)[:len(reads)]
+
+    def map_batch_ctx_resident(self, src: ResidentReads, ids: Sequence[int], params: Params, intervals=None, min_swatscor=None, prev_max=None,
+                               fine_index: bool = False, raw_alignments: bool = False, seed_range=None, allow_read_errors: bool = False):
+        """map_batch_ctx over reads of two batches resident in HBM (smaltgpu_map_batch_ctx_resident): read i of the round is read
+        ids[i] >> 1 of batch ids[i] & 1 of `src`; the context arguments are indexed like ids.
+        -> (results, stats, cand_first flags per result)"""
+        n = len(ids)
+        ctx, keep = self._ctx(n, intervals, min_swatscor, prev_max, fine_index, raw_alignments, seed_range)
+        arr = (C.c_uint32 * max(1, n))(*ids)
+        out = BatchOut()
+        rv = lib().smaltgpu_map_batch_ctx_resident(self.h, C.byref(src), arr, n, C.byref(params), C.byref(ctx), C.byref(out))
+        if rv != 0 and not (allow_read_errors and rv in (ECAP, EINTERNAL, ESCORE, ECPLX) and out.nreads == n):
+            _check(rv)
+        res, stats = self._unpack(out)
+        cf = [[bool(out.res[j].reverse & 2) for j in range(out.res_off[i], out.res_off[i + 1])] for i in range(n)]
+        return res, stats, cf
+
+    def hit_totals_resident(self, src: ResidentReads, ids: Sequence[int], params: Params) -> List[int]:
+        """hit_totals of the reads `ids` of two batches resident in HBM (smaltgpu_hit_totals_resident)."""
+        n = len(ids)
+        arr = (C.c_uint32 * max(1, n))(*ids)
+        out = (C.c_uint32 * max(1, n))()
+        _check(lib().smaltgpu_hit_totals_resident(self.h, C.byref(src), arr, n, C.byref(params), out))
+        return list(out)[:n]
+
+    def map_pairs_resident(self, src: ResidentReads, npairs: int, params: Params, popts: PairOpts, bases1=None, quals1=None, bases2=None, quals2=None,
+                           pairs_handle=None):
+        """smaltgpu_map_pairs_resident: rmapPair for the first npairs pairs of the resident batches `src`; bases / quals are the
+        optional host copies (numpy uint8, indexed by src.read_off).  -> as map_pairs_raw"""
+        L = lib()
+        h = pairs_handle or C.c_void_p(L.smaltgpu_pairs_create())
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        _check(L.smaltgpu_map_pairs_resident(self.h, C.byref(src), ptr(bases1), ptr(quals1), ptr(bases2), ptr(quals2), npairs, C.byref(params), C.byref(popts), h))
+        return (h,) + self._pairs_info(h)
+
+    @staticmethod
+    def _pairs_info(h):
+        import numpy as np
+        npairs = C.c_uint32()
+        info = C.POINTER(PairInfo)()
+        calls = (C.c_uint64 * 4)()
+        ms = (C.c_double * 4)()
+        _check(lib().smaltgpu_pairs_info(h, C.byref(npairs), C.byref(info), calls, ms))
+        arr = np.ctypeslib.as_array(C.cast(info, C.POINTER(C.c_uint8)), shape=(max(1, npairs.value), 6))[:npairs.value]
+        return arr, list(calls), list(ms)
+
+    def set_host_threads(self, nthreads: int):
+        """host threads for the mapper's own host work: the copy of a batch's results into read order in fetch_end"""
+        _check(lib().smaltgpu_mapper_set_host_threads(self.h, nthreads))
+
+    def remap_batches(self) -> int:
+        """diagnostic: device batches run so far to map reads again that did not fit a work pool"""
+        n = C.c_uint64()
+        _check(lib().smaltgpu_mapper_remap_batches(self.h, C.byref(n)))
+        return n.value
 
     def map_pairs_raw(self, bases1, off1, quals1, bases2, off2, quals2, params: Params, popts: PairOpts, pairs_handle=None):
         """smaltgpu_map_pairs on contiguous host arrays (numpy uint8 bases / uint64 offsets per mate file): rmapPair for a block.
@@ -710,6 +778,19 @@ class Mapper:
         out = BatchOut()
         _check(lib().smaltgpu_fetch_end(self.h, C.byref(out)))
         return out
+
+    def fetch_end_rc(self):
+        """fetch_end -> (return code, BatchOut) without raising: a read error (ECAP, EINTERNAL, ESCORE, ECPLX) comes with the batch
+        filled and the code of every read in stat[].errcode; any other code with whatever the call left in the BatchOut"""
+        out = BatchOut()
+        return lib().smaltgpu_fetch_end(self.h, C.byref(out)), out
+
+    def fetch_results_rc(self):
+        """fetch_results -> (return code, BatchOut) without raising, as fetch_end_rc"""
+        out = BatchOut()
+        return lib().smaltgpu_fetch_results(self.h, C.byref(out)), out
+
+    unpack = _unpack                        # (results, stats) of a BatchOut, as map_batch returns them
 
     def timers(self):
         ms = (C.c_double * 32)()

@@ -1078,6 +1078,12 @@ extern "C" int smaltgpu_mapper_set_host_threads(smaltgpu_mapper *m, int nthreads
   return SMALTGPU_OK;
 }
 
+extern "C" int smaltgpu_mapper_remap_batches(const smaltgpu_mapper *m, uint64_t *nbatches) {
+  if (!m || !nbatches) return fail(SMALTGPU_EARG, "null argument");
+  *nbatches = m->remap_batches;
+  return SMALTGPU_OK;
+}
+
 extern "C" int smaltgpu_mapper_set_history(smaltgpu_mapper *m, int on) {
   if (!m) return fail(SMALTGPU_EARG, "null mapper");
   m->history = on != 0;
