@@ -12,7 +12,7 @@
 //     compaction over "first segment of a candidate" flags reproduces exactly;
 //   * max_cover / max2nd_cover are order-free (largest and second largest DISTINCT cover).
 // The per-strand working set (hit words, seeds, segments, regions) lives in LDS when the strand
-// has at most CANDS_LDS_HITS hits, else in the HBM slot.
+// has at most CANDS_LDS_HITS hits, else in the HBM slot.  The wave's scans, reductions and key sorts are smg_exec.h's.
 // `file:line` citations refer to the reference tree (SMALT 0.7.6, src/).
 #pragma once
 #include "smg_stages.hpp"
@@ -172,18 +172,7 @@ SMG_HD inline int strand_cands(StrandWork<IT> &w, uint32_t n, bool is_reverse, b
   if (!n) return 0;
   unsigned long long t0 = phase_clock(), t1;
 #define SMG_PH(i) { t1 = phase_clock(); ph[i] += t1 - t0; t0 = t1; }
-  if (!presorted) {                              // (k_hits delivers the keys of a strand in order)
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (n <= 1024 && (StrandWork<IT>::L || n <= 256)) {   // keys sorted in registers: the LDS working set, and short runs of the HBM one (the
-    if (n <= 256) wave_sort_u64_reg<4>(w.dat, n);       // few hits of a restricted call: ten round trips to HBM with the network in memory)
-    else if (n <= 512) wave_sort_u64_reg<8>(w.dat, n);
-    else wave_sort_u64_reg<16>(w.dat, n);
-  } else if (!StrandWork<IT>::L) wave_sort_u64_chunked(w.dat, n);                  // longer runs in HBM (exhaustive search): chunks of 1024 keys in registers
-  else wave_sort_u64(w.dat, n);
-#else
-  wave_sort_u64(w.dat, n);
-#endif
-  }
+  if (!presorted) wave_sort_keys<!StrandWork<IT>::L>(w.dat, n);      // (k_hits delivers the keys of a strand in order)
   SMG_SYNC();
   SMG_PH(2)
   uint32_t max_dshift = (uint32_t)(k * SEGMENTING_DIFFSHIFT / s) & 0xffffu;     // segment.c:426-429
@@ -699,17 +688,9 @@ SMG_HD inline void stage_hits(const Batch &b, const DevIndex &ix, const MapPar &
         take = nh > 0;
       }
     }
-    uint32_t incl = nh;
-#if defined(__HIP_DEVICE_COMPILE__)
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += v; }
-#endif
+    const uint32_t pfx = wave_scan_add_u32(nh, total);
     const uint32_t slot = compact_slot(take, nlist);
-    if (take) { g_pfx[slot] = total + incl - nh; g_poff[slot] = poff; g_qo[slot] = qo; g_len[slot] = nh; g_cur[slot] = 0; }
-#if defined(__HIP_DEVICE_COMPILE__)
-    total += (uint32_t)__shfl((int)incl, 63);
-#else
-    total += incl;
-#endif
+    if (take) { g_pfx[slot] = pfx; g_poff[slot] = poff; g_qo[slot] = qo; g_len[slot] = nh; g_cur[slot] = 0; }
   }
   SMG_SYNC();
   if (!total) { run.mode = HITRUN_SORTED; SMG_LANE0 { b.hitrun[rs] = run; } return; }
@@ -725,14 +706,7 @@ SMG_HD inline void stage_hits(const Batch &b, const DevIndex &ix, const MapPar &
   SMG_PH(0)
   auto sort_and_write = [&](uint32_t n, uint32_t at) {
     const unsigned long long ts0 = phase_clock();
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (n <= 256) wave_sort_u64_reg<4>(dat, n);
-    else if (n <= 512) wave_sort_u64_reg<8>(dat, n);
-    else if (n <= 1024) wave_sort_u64_reg<16>(dat, n);
-    else wave_sort_u64(dat, n);
-#else
-    wave_sort_u64(dat, n);
-#endif
+    wave_sort_keys<false>(dat, n);
     SMG_SYNC();
     SMG_PAR_CHUNKS(base, n) { const uint32_t i = base + SMG_LANE; if (i < n) out[at + i] = dat[i]; }
     SMG_SYNC();
@@ -890,16 +864,8 @@ SMG_HD inline void stage_hits(const Batch &b, const DevIndex &ix, const MapPar &
       SMG_PAR_CHUNKS(base, nlist) {
         const uint32_t l = base + SMG_LANE;
         const uint32_t cnt = l < nlist ? g_pfx[l] : 0u;
-        uint32_t incl = cnt;
-#if defined(__HIP_DEVICE_COMPILE__)
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += v; }
-#endif
-        if (l < nlist) { g_pfx[l] = run_tot + incl - cnt; if (cnt && run_tot + incl - cnt < room + nlist) marks[run_tot + incl - cnt] = (uint16_t)(l + 1); }
-#if defined(__HIP_DEVICE_COMPILE__)
-        run_tot += (uint32_t)__shfl((int)incl, 63);
-#else
-        run_tot += incl;
-#endif
+        const uint32_t at = wave_scan_add_u32(cnt, run_tot);
+        if (l < nlist) { g_pfx[l] = at; if (cnt && at < room + nlist) marks[at] = (uint16_t)(l + 1); }
       }
       SMG_SYNC();
       const uint32_t sq_lo = seqbyseq ? (uint32_t)(prev_bound >> KEY_DIAGBITS) : 0u;
@@ -1077,20 +1043,11 @@ SMG_HD inline uint32_t stage_cands_v2(const Batch &b, const DevIndex &ix, const 
             qo = sd.qoffs;
           }
         }
-        uint32_t incl = cnt;
-#if defined(__HIP_DEVICE_COMPILE__)
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += v; }
-#endif
-        const uint32_t at = nkeys + incl - cnt;
+        const uint32_t at = wave_scan_add_u32(cnt, nkeys);
         if (at + cnt <= x.hcap_strand) {
           for (uint32_t j = 0; j < cnt; j++)
             wg.dat[at + j] = ((uint64_t)g << (KEY_DIAGBITS + KEY_QBITS)) | (hit_diag_m(st != 0, posp[a + j], qo, smagic) << KEY_QBITS) | qo;
         } else ovf = true;
-#if defined(__HIP_DEVICE_COMPILE__)
-        nkeys += (uint32_t)__shfl((int)incl, 63);
-#else
-        nkeys += incl;
-#endif
       }
       if (wave_any(ovf)) { err = SMG_ERR_CAP; site = __LINE__; break; }
       SMG_SYNC();
@@ -1257,17 +1214,9 @@ SMG_HD inline uint32_t stage_cands_v2(const Batch &b, const DevIndex &ix, const 
             take = nh > 0;
           }
         }
-        uint32_t incl = nh;
-#if defined(__HIP_DEVICE_COMPILE__)
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += v; }
-#endif
+        const uint32_t pfx = wave_scan_add_u32(nh, total);
         const uint32_t slot = compact_slot(take, nlist);
-        if (take) { g_pfx[slot] = total + incl - nh; g_poff[slot] = poff; g_qo[slot] = qo; g_len[slot] = nh; }
-#if defined(__HIP_DEVICE_COMPILE__)
-        total += (uint32_t)__shfl((int)incl, 63);
-#else
-        total += incl;
-#endif
+        if (take) { g_pfx[slot] = pfx; g_poff[slot] = poff; g_qo[slot] = qo; g_len[slot] = nh; }
       }
       SMG_SYNC();
     }
@@ -1353,16 +1302,8 @@ SMG_HD inline uint32_t stage_cands_v2(const Batch &b, const DevIndex &ix, const 
               cnt = lo < hi ? lo : hi;
             }
           }
-          uint32_t incl = cnt;
-#if defined(__HIP_DEVICE_COMPILE__)
-          for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += v; }
-#endif
-          if (l < nlist) { g_pfx[l] = cnt_tot + incl - cnt; if (cnt && cnt_tot + incl - cnt < room + nlist) marks[cnt_tot + incl - cnt] = (uint16_t)(l + 1); }
-#if defined(__HIP_DEVICE_COMPILE__)
-          cnt_tot += (uint32_t)__shfl((int)incl, 63);
-#else
-          cnt_tot += incl;
-#endif
+          const uint32_t at = wave_scan_add_u32(cnt, cnt_tot);
+          if (l < nlist) { g_pfx[l] = at; if (cnt && at < room + nlist) marks[at] = (uint16_t)(l + 1); }
         }
         SMG_SYNC();
         const unsigned long long tb0 = phase_clock();
@@ -1585,16 +1526,9 @@ SMG_HD inline uint32_t stage_cands_v2(const Batch &b, const DevIndex &ix, const 
       uint32_t run = 0;
       SMG_PAR_CHUNKS(base, nbins) {
         const uint32_t i = base + SMG_LANE;
-        uint32_t incl = i < nbins ? hist[i] : 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += v; }
-#endif
-        if (i < nbins) hist[i] = run + incl;
-#if defined(__HIP_DEVICE_COMPILE__)
-        run += (uint32_t)__shfl((int)incl, 63);
-#else
-        run += incl;
-#endif
+        const uint32_t v = i < nbins ? hist[i] : 0;
+        const uint32_t incl = wave_scan_add_u32(v, run) + v;
+        if (i < nbins) hist[i] = incl;
       }
     } else SMG_LANE0 { uint32_t c = 0; for (int v = 0; v < WSORT_NBINS; v++) { c += hist[v]; hist[v] = c; } }
     SMG_SYNC();

@@ -9,6 +9,10 @@
 // On the device SMG_NLANES = 64.  The same source also compiles for the host with
 // SMG_NLANES = 1 (tests/hostemu): that build exists to unit-test this logic on a machine
 // without a GPU and is never part of libsmaltgpu.so.
+//
+// Below the macros: the wave primitives (compaction, sums, minima and maxima, ballot, the add scan and the running maximum),
+// each one function with its device and host form inside, so that stage code holds no #if; then the sort of 64-bit keys
+// (one network over memory, one over registers, the forms built from them and wave_sort_keys, which picks a form).
 #pragma once
 #include <stdint.h>
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -82,6 +86,13 @@ SMG_HD inline uint32_t wave_max_u32(uint32_t v) {
   return v;
 }
 
+SMG_HD inline uint32_t wave_min_u32(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  for (int o = 32; o > 0; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)v, o); if (u < v) v = u; }
+#endif
+  return v;
+}
+
 SMG_HD inline uint64_t wave_min_u64(uint64_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
   for (int o = 32; o > 0; o >>= 1) {
@@ -99,6 +110,31 @@ SMG_HD inline bool wave_any(bool f) {
 #else
   return f;
 #endif
+}
+
+// one bit per lane (the host build's one lane is bit 0)
+SMG_HD inline unsigned long long wave_ballot(bool f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __ballot(f);
+#else
+  return f ? 1ull : 0ull;
+#endif
+}
+
+// Add scan over the lanes, continued from the wave-uniform running `total` (the sum of everything before lane 0): returns the
+// lane's exclusive prefix, total included, and advances the total by the wave's sum.  The inclusive prefix is the result + v.
+SMG_HD inline uint32_t wave_scan_add_u32(uint32_t v, uint32_t &total) {
+  uint32_t incl = v;
+#if defined(__HIP_DEVICE_COMPILE__)
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += u; }
+#endif
+  const uint32_t excl = total + incl - v;
+#if defined(__HIP_DEVICE_COMPILE__)
+  total += (uint32_t)__shfl((int)incl, 63);
+#else
+  total += incl;
+#endif
+  return excl;
 }
 
 // inclusive running maximum over the lanes, continued from `carry` (the maximum of everything before lane 0); returns the
@@ -130,57 +166,70 @@ SMG_HD inline uint32_t bcast_lane0(uint32_t v) {
 #endif
 }
 
-// In-place ascending sort of n 64-bit keys by the whole wave: bitonic network in its normalised form (every
-// comparator puts the smaller key at the lower index: the first step of a merge pairs i with its mirror
-// image in the block, the others pair i with i + j).  Keys beyond n are virtual +inf: a comparator that
-// touches one never swaps, so no padding is stored and only comparators below n are visited.
+// ---------------------------------------------------------------------------------------------------------------
+// Ascending sort of 64-bit keys by the whole wave: ONE bitonic network in its normalised form (every comparator puts the
+// smaller key at the lower index: the first step of a merge pairs i with its mirror image in the block of k, the others pair
+// i with i + j), written once over memory (sort_mirror_mem, sort_halfclean_mem) and once over registers (sort_network_reg).
+// Keys beyond n are virtual +inf: a comparator that touches one never swaps, so no padding is stored and only comparators
+// below n are visited.  The forms put the two together:
+//   wave_sort_u64          every step in memory (LDS or HBM, by the pointer type)
+//   wave_sort_u64_reg<E>   up to 64 * E keys, the whole network in registers
+//   wave_sort_u64_chunked  runs in HBM: chunks of 1024 keys in registers, the steps that span chunks in memory
+//   wave_sort_keys         which of them a stage takes for n keys
+// Neither memory step ends with a barrier: the callers differ in what they need there.
+
+// One step over memory.  Each lane loads the operands of up to four comparators before it stores any: the step is bound by the
+// memory's latency, and four independent round trips overlap.
+template <class P>
+SMG_HD inline void sort_mirror_mem(P a, uint32_t n, uint32_t k) {          // first step of the merge into blocks of k
+  const uint32_t h = k >> 1;
+  const uint32_t tmax = (n / k) * h + ((n % k) < h ? (n % k) : h);
+  for (uint32_t t0 = 0; t0 < tmax; t0 += 4 * SMG_NLANES) {
+    uint32_t ii[4], pp[4];
+    uint64_t x[4], y[4];
+    bool on[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const uint32_t t = t0 + (uint32_t)u * SMG_NLANES + SMG_LANE;
+      const uint32_t blk = t / h, off = t % h;
+      ii[u] = blk * k + off; pp[u] = blk * k + (k - 1 - off);
+      on[u] = t < tmax && pp[u] < n;
+      if (on[u]) { x[u] = a[ii[u]]; y[u] = a[pp[u]]; }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) if (on[u] && x[u] > y[u]) { a[ii[u]] = y[u]; a[pp[u]] = x[u]; }
+  }
+}
+template <class P>
+SMG_HD inline void sort_halfclean_mem(P a, uint32_t n, uint32_t j) {       // half-cleaner: i with i + j
+  const uint32_t tmax = (n / (2 * j)) * j + ((n % (2 * j)) < j ? (n % (2 * j)) : j);
+  for (uint32_t t0 = 0; t0 < tmax; t0 += 4 * SMG_NLANES) {
+    uint32_t ii[4];
+    uint64_t x[4], y[4];
+    bool on[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const uint32_t t = t0 + (uint32_t)u * SMG_NLANES + SMG_LANE;
+      ii[u] = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+      on[u] = t < tmax && (ii[u] | j) < n;
+      if (on[u]) { x[u] = a[ii[u]]; y[u] = a[ii[u] | j]; }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) if (on[u] && x[u] > y[u]) { a[ii[u]] = y[u]; a[ii[u] | j] = x[u]; }
+  }
+}
+
+// In place, n keys, every step in memory.
 template <class P>
 SMG_HD inline void wave_sort_u64(P a, uint32_t n) {
   if (n < 2) return;
 #if defined(__HIP_DEVICE_COMPILE__)
   uint32_t np = 1;
   while (np < n) np <<= 1;
-  // Each step loads the operands of up to four comparators per lane before it stores any: the step is bound by
-  // LDS latency, and four independent round trips overlap.
   for (uint32_t k = 2; k <= np; k <<= 1) {
-    const uint32_t h = k >> 1;
-    {                                                           // mirror step
-      const uint32_t tmax = (n / k) * h + ((n % k) < h ? (n % k) : h);
-      for (uint32_t t0 = 0; t0 < tmax; t0 += 4 * SMG_NLANES) {
-        uint32_t ii[4], pp[4];
-        uint64_t x[4], y[4];
-        bool on[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const uint32_t t = t0 + (uint32_t)u * SMG_NLANES + SMG_LANE;
-          const uint32_t blk = t / h, off = t % h;
-          ii[u] = blk * k + off; pp[u] = blk * k + (k - 1 - off);
-          on[u] = t < tmax && pp[u] < n;
-          if (on[u]) { x[u] = a[ii[u]]; y[u] = a[pp[u]]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) if (on[u] && x[u] > y[u]) { a[ii[u]] = y[u]; a[pp[u]] = x[u]; }
-      }
-      SMG_SYNC();
-    }
-    for (uint32_t j = h >> 1; j > 0; j >>= 1) {
-      const uint32_t tmax = (n / (2 * j)) * j + ((n % (2 * j)) < j ? (n % (2 * j)) : j);
-      for (uint32_t t0 = 0; t0 < tmax; t0 += 4 * SMG_NLANES) {
-        uint32_t ii[4];
-        uint64_t x[4], y[4];
-        bool on[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const uint32_t t = t0 + (uint32_t)u * SMG_NLANES + SMG_LANE;
-          ii[u] = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-          on[u] = t < tmax && (ii[u] | j) < n;
-          if (on[u]) { x[u] = a[ii[u]]; y[u] = a[ii[u] | j]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) if (on[u] && x[u] > y[u]) { a[ii[u]] = y[u]; a[ii[u] | j] = x[u]; }
-      }
-      SMG_SYNC();
-    }
+    sort_mirror_mem(a, n, k);
+    SMG_SYNC();
+    for (uint32_t j = k >> 2; j > 0; j >>= 1) { sort_halfclean_mem(a, n, j); SMG_SYNC(); }
   }
 #else
   // host build: any correct sort gives the same array (keys are plain integers)
@@ -189,11 +238,6 @@ SMG_HD inline void wave_sort_u64(P a, uint32_t n) {
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// The same network with the keys in registers, for arrays of at most 64 * E keys in LDS.  Lane l holds the logical
-// elements E * l .. E * l + E - 1 (which unsorted key starts where is free, so the load is coalesced); comparators
-// whose span stays below E are compare-exchanges between a lane's own registers, the others pair register r of a lane
-// with register r (mirror step: E - 1 - r) of the lane at distance span / E and keep the smaller or the larger key
-// by side.  34 of the 55 steps of a 1024-key sort touch neither LDS nor another lane.
 __device__ inline uint64_t shfl_xor_u64(uint64_t v, int mask) {
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
   return ((uint64_t)hi << 32) | lo;
@@ -206,21 +250,21 @@ __device__ inline uint64_t shfl_xor_u64(uint64_t v, int mask) {
 // and compares again: nine vector instructions per exchange.  This form is one v_cmp_lt_u64, one s_xor_b64 with the step's lane
 // mask (scalar unit) and the two selects of the key's halves (profiles/hits_sort_exchange_static.txt).
 __device__ inline uint64_t keep_side_u64(uint64_t v, uint64_t o, bool upper) { return ((o < v) != upper) ? o : v; }
-template <int E, class P>
-__device__ inline void wave_sort_u64_reg(P a, uint32_t n) {
-  if (n < 2) return;
-  const uint32_t lane = threadIdx.x;
-  uint64_t v[E];
+// compare-exchange between two registers of one lane
+__device__ inline void order_u64(uint64_t &lo, uint64_t &hi) { const uint64_t x = lo, y = hi; const bool sw = x > y; lo = sw ? y : x; hi = sw ? x : y; }
+
+// The whole network over 64 * E keys in registers.  Lane l holds the logical elements E * l .. E * l + E - 1 (which unsorted
+// key starts where is free, so the callers' loads are coalesced); comparators whose span stays below E are compare-exchanges
+// between a lane's own registers, the others pair register r of a lane with register r (mirror step: E - 1 - r) of the lane
+// at distance span / E and keep the smaller or the larger key by side.  34 of the 55 steps of a 1024-key sort touch neither
+// memory nor another lane.
+template <int E>
+__device__ inline void sort_network_reg(uint64_t (&v)[E], uint32_t lane) {
 #pragma unroll
-  for (int r = 0; r < E; r++) { const uint32_t idx = (uint32_t)r * 64u + lane; v[r] = idx < n ? a[idx] : ~0ull; }
-#pragma unroll
-  for (int k = 2; k <= 64 * E; k <<= 1) {              // the whole network: the coalesced load spreads the keys over all lanes
+  for (int k = 2; k <= 64 * E; k <<= 1) {
     if (k <= E) {                                      // mirror step inside the lane
 #pragma unroll
-      for (int r = 0; r < E; r++) {
-        const int q = r ^ (k - 1);
-        if (r < q) { const uint64_t x = v[r], y = v[q]; const bool sw = x > y; v[r] = sw ? y : x; v[q] = sw ? x : y; }
-      }
+      for (int r = 0; r < E; r++) { const int q = r ^ (k - 1); if (r < q) order_u64(v[r], v[q]); }
     } else {                                           // mirror step across lanes
       const int m = k / E - 1;
       const bool upper = (lane & (uint32_t)(k / (2 * E))) != 0;
@@ -234,9 +278,7 @@ __device__ inline void wave_sort_u64_reg(P a, uint32_t n) {
     for (int j = k / 4; j >= 1; j >>= 1) {
       if (j < E) {
 #pragma unroll
-        for (int r = 0; r < E; r++) {
-          if (!(r & j)) { const uint64_t x = v[r], y = v[r | j]; const bool sw = x > y; v[r] = sw ? y : x; v[r | j] = sw ? x : y; }
-        }
+        for (int r = 0; r < E; r++) { if (!(r & j)) order_u64(v[r], v[r | j]); }
       } else {
         const int m = j / E;
         const bool upper = (lane & (uint32_t)m) != 0;
@@ -245,6 +287,19 @@ __device__ inline void wave_sort_u64_reg(P a, uint32_t n) {
       }
     }
   }
+}
+
+// In place, at most 64 * E keys (in LDS, or a short run in HBM): coalesced load, the network, store in order.
+// Not inlined, which is what the compiler chose for every caller anyway: said here, it no longer depends on how the call is
+// wrapped (behind wave_sort_keys the short HBM form went inline into k_cands and the tightest instance spilled more).
+template <int E, class P>
+__device__ __noinline__ void wave_sort_u64_reg(P a, uint32_t n) {
+  if (n < 2) return;
+  const uint32_t lane = threadIdx.x;
+  uint64_t v[E];
+#pragma unroll
+  for (int r = 0; r < E; r++) { const uint32_t idx = (uint32_t)r * 64u + lane; v[r] = idx < n ? a[idx] : ~0ull; }
+  sort_network_reg<E>(v, lane);
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < E; r++) { const uint32_t i = (uint32_t)E * lane + (uint32_t)r; if (i < n) a[i] = v[r]; }
@@ -270,9 +325,7 @@ __device__ inline void sort_chunk_1024(P a, uint32_t base, uint32_t n) {
 #pragma unroll
     for (int j = 512; j >= 64; j >>= 1) {
 #pragma unroll
-      for (int r = 0; r < E; r++) {
-        if (!(r & (j / 64))) { const uint64_t x = v[r], y = v[r | (j / 64)]; const bool sw = x > y; v[r] = sw ? y : x; v[r | (j / 64)] = sw ? x : y; }
-      }
+      for (int r = 0; r < E; r++) { if (!(r & (j / 64))) order_u64(v[r], v[r | (j / 64)]); }
     }
 #pragma unroll
     for (int j = 32; j >= 1; j >>= 1) {
@@ -284,42 +337,12 @@ __device__ inline void sort_chunk_1024(P a, uint32_t base, uint32_t n) {
     for (int r = 0; r < E; r++) { const uint32_t idx = base + (uint32_t)r * 64u + lane; if (idx < n) a[idx] = v[r]; }
     return;
   }
-#pragma unroll
-  for (int k = 2; k <= 1024; k <<= 1) {
-    if (k <= E) {
-#pragma unroll
-      for (int r = 0; r < E; r++) {
-        const int q = r ^ (k - 1);
-        if (r < q) { const uint64_t x = v[r], y = v[q]; const bool sw = x > y; v[r] = sw ? y : x; v[q] = sw ? x : y; }
-      }
-    } else {
-      const int m = k / E - 1;
-      const bool upper = (lane & (uint32_t)(k / (2 * E))) != 0;
-      uint64_t pv[E];
-#pragma unroll
-      for (int r = 0; r < E; r++) pv[r] = shfl_xor_u64(v[E - 1 - r], m);
-#pragma unroll
-      for (int r = 0; r < E; r++) { v[r] = keep_side_u64(v[r], pv[r], upper); }
-    }
-#pragma unroll
-    for (int j = k / 4; j >= 1; j >>= 1) {
-      if (j < E) {
-#pragma unroll
-        for (int r = 0; r < E; r++) {
-          if (!(r & j)) { const uint64_t x = v[r], y = v[r | j]; const bool sw = x > y; v[r] = sw ? y : x; v[r | j] = sw ? x : y; }
-        }
-      } else {
-        const int m = j / E;
-        const bool upper = (lane & (uint32_t)m) != 0;
-#pragma unroll
-        for (int r = 0; r < E; r++) { v[r] = keep_side_u64(v[r], shfl_xor_u64(v[r], m), upper); }
-      }
-    }
-  }
+  sort_network_reg<E>(v, lane);
 #pragma unroll
   for (int r = 0; r < E; r++) { const uint32_t idx = base + (uint32_t)E * lane + (uint32_t)r; if (idx < n) a[idx] = v[r]; }
 }
 
+// (not inlined: one function, fitted to all its callers -- see smg_sortraw.hip)
 template <class P>
 __device__ __noinline__ void wave_sort_u64_chunked(P a, uint32_t n) {
   constexpr uint32_t C = 1024;
@@ -329,43 +352,11 @@ __device__ __noinline__ void wave_sort_u64_chunked(P a, uint32_t n) {
   uint32_t np = C;
   while (np < n) np <<= 1;
   for (uint32_t k = 2 * C; k <= np; k <<= 1) {
-    const uint32_t h = k >> 1;
-    {                                                           // mirror step (pairs i with its mirror image in the block of k)
-      const uint32_t tmax = (n / k) * h + ((n % k) < h ? (n % k) : h);
-      for (uint32_t t0 = 0; t0 < tmax; t0 += 4 * SMG_NLANES) {
-        uint32_t ii[4], pp[4];
-        uint64_t x[4], y[4];
-        bool on[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const uint32_t t = t0 + (uint32_t)u * SMG_NLANES + SMG_LANE;
-          const uint32_t blk = t / h, off = t % h;
-          ii[u] = blk * k + off; pp[u] = blk * k + (k - 1 - off);
-          on[u] = t < tmax && pp[u] < n;
-          if (on[u]) { x[u] = a[ii[u]]; y[u] = a[pp[u]]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) if (on[u] && x[u] > y[u]) { a[ii[u]] = y[u]; a[pp[u]] = x[u]; }
-      }
-      __threadfence_block();
-      __syncthreads();
-    }
-    for (uint32_t j = h >> 1; j >= C; j >>= 1) {                // half-cleaners that span chunks
-      const uint32_t tmax = (n / (2 * j)) * j + ((n % (2 * j)) < j ? (n % (2 * j)) : j);
-      for (uint32_t t0 = 0; t0 < tmax; t0 += 4 * SMG_NLANES) {
-        uint32_t ii[4];
-        uint64_t x[4], y[4];
-        bool on[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const uint32_t t = t0 + (uint32_t)u * SMG_NLANES + SMG_LANE;
-          ii[u] = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-          on[u] = t < tmax && (ii[u] | j) < n;
-          if (on[u]) { x[u] = a[ii[u]]; y[u] = a[ii[u] | j]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) if (on[u] && x[u] > y[u]) { a[ii[u]] = y[u]; a[ii[u] | j] = x[u]; }
-      }
+    sort_mirror_mem(a, n, k);
+    __threadfence_block();
+    __syncthreads();
+    for (uint32_t j = k >> 2; j >= C; j >>= 1) {                // half-cleaners that span chunks
+      sort_halfclean_mem(a, n, j);
       __threadfence_block();
       __syncthreads();
     }
@@ -375,5 +366,23 @@ __device__ __noinline__ void wave_sort_u64_chunked(P a, uint32_t n) {
   }
 }
 #endif
+
+// The form a stage takes for n unsorted keys.  Up to 256 keys go to registers wherever they lie (the few hits of a restricted
+// call in the HBM working set: ten round trips to HBM with the network in memory); beyond that the LDS arrays take the wider
+// register forms up to 1024 keys and the network in LDS above, and only the HBM working set (HBM = true: longer runs of the
+// exhaustive search) takes the chunked sort.  P keeps the array's address space, so LDS arrays are sorted with ds_* code.
+template <bool HBM, class P>
+SMG_HD inline void wave_sort_keys(P a, uint32_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (n <= 1024 && (!HBM || n <= 256)) {
+    if (n <= 256) wave_sort_u64_reg<4>(a, n);
+    else if (n <= 512) wave_sort_u64_reg<8>(a, n);
+    else wave_sort_u64_reg<16>(a, n);
+  } else if (HBM) wave_sort_u64_chunked(a, n);
+  else wave_sort_u64(a, n);
+#else
+  wave_sort_u64(a, n);
+#endif
+}
 
 }  // namespace smg

@@ -305,16 +305,8 @@ SMG_HD inline uint32_t stage_seed(const Batch &b, const DevIndex &ix, const MapP
       const uint32_t i = base + SMG_LANE;
       uint32_t v = 0;
       if (i < nseeds) { v = x.kv[i] >> SEED_IDXBITS; x.key[i] = v; x.sidx[i] = x.kv[i] & ((1u << SEED_IDXBITS) - 1u); x.qbr[i] = x.sqoffs[x.sidx[i]]; }
-      uint32_t incl = v;
-#if defined(__HIP_DEVICE_COMPILE__)
-      for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)incl, o); if ((int)SMG_LANE >= o) incl += u; }
-#endif
-      if (i < nseeds) x.wk[i] = run + incl;
-#if defined(__HIP_DEVICE_COMPILE__)
-      run += (uint32_t)__shfl((int)incl, 63);
-#else
-      run += incl;
-#endif
+      const uint32_t incl = wave_scan_add_u32(v, run) + v;
+      if (i < nseeds) x.wk[i] = incl;
     }
     SMG_SYNC();
     uint32_t mincover = (uint32_t)(HITINFO_MINCOVER_KMER * k + s);
@@ -325,9 +317,7 @@ SMG_HD inline uint32_t stage_seed(const Batch &b, const DevIndex &ix, const MapP
     // n = first rank whose inclusive prefix exceeds HASH_MAXNHITS (hashhit.c:822-827), n_seeds if none
     uint32_t nbud = nseeds;
     SMG_PAR_CHUNKS(base, nseeds) { const uint32_t i = base + SMG_LANE; if (i < nseeds && x.wk[i] > (uint32_t)HASH_MAXNHITS && i < nbud) nbud = i; }
-#if defined(__HIP_DEVICE_COMPILE__)
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)nbud, o); if (u < nbud) nbud = u; }
-#endif
+    nbud = wave_min_u32(nbud);
     uint32_t nmax = nbud;
     // the ranks of every sampling frame as a list of its own (all lanes: a seed's frame, its place in the frame's list by
     // ballot), so that the lane of a frame walks its ~ n/s seeds and not all n (the walk was 40 % of the kernel)
@@ -1455,11 +1445,7 @@ SMG_HD inline void stage_align(const Batch &b, const DevIndex &ix, const MapPar 
   for (uint32_t cbase = 0; cbase < ncand && !x.state[S_ERR]; cbase += SMG_NLANES) {
    const uint32_t cmy = cbase + SMG_LANE;
    const bool cpass = cmy < ncand && rc[cmy].swscor >= ctl.min_swatscor;
-#if defined(__HIP_DEVICE_COMPILE__)
-   unsigned long long cmask = __ballot(cpass);
-#else
-   unsigned long long cmask = cpass ? 1ull : 0ull;
-#endif
+   unsigned long long cmask = wave_ballot(cpass);
    while (cmask) {
     const uint32_t ci = cbase + (uint32_t)__builtin_ctzll(cmask);
     cmask &= cmask - 1ull;

@@ -4,9 +4,9 @@ tests/test_gpu_score_route.py checks what the stage left in the pool).  A case i
 reads cut from it, and a mapper shape; all calls run without FLG_BEST, so that the oracle scores every ranked candidate and its
 candidate list is the ranked list of the pool.
 
-The two copies of S7's listing rule.  Every instance of k_cands compiles both: smg_cands.hpp:1669 is the tail of stage_cands_v2 (the
-wave-parallel form), smg_stages.hpp:705 the tail of stage_cands (the sequential form).  Which one a read runs is decided per read at
-run time by cands_v2_applicable (smg_cands.hpp:605): the wave-parallel form whenever the call is sequence by sequence
+The two copies of S7's listing rule.  Every instance of k_cands compiles both: one is the tail ("S7") of stage_cands_v2 in smg_cands.hpp (the
+wave-parallel form), the other the tail of stage_cands in smg_stages.hpp (the sequential form).  Which one a read runs is decided per
+read at run time by cands_v2_applicable (smg_cands.hpp): the wave-parallel form whenever the call is sequence by sequence
 (FLG_SEQBYSEQ, the default below 512 sequences), restricted to intervals, or has min_cover < k + s; the sequential form otherwise.
 Every case below runs the first copy; `w248_seq` and `long_mapper_short_reads_seq` repeat two workloads with FLG_SEQBYSEQ cleared and
 min_cover = k + s, which is the second copy (their windows lie in the concatenated set, sqidx = -1).

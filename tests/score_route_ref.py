@@ -115,7 +115,7 @@ def plan(cands, qlens, has_n, geo, par, scorer=None):
     err0 = [bool(c.get("err")) for c in cands]
     banded = [(not err0[i]) and is_banded(cands[i], q[i]) for i in range(n)]
     in_tile = [q[i] <= tile_qmax and w[i] <= SW_FULL_WMAX for i in range(n)]
-    # S7's lists (smg_cands.hpp:1669-1681, smg_stages.hpp:705-717)
+    # S7's lists (the tails of stage_cands_v2 in smg_cands.hpp and of stage_cands in smg_stages.hpp)
     strip_listed = [(not err0[i]) and ((not banded[i] and not in_tile[i]) or (banded[i] and q[i] > BAND_WAVE_QMIN)) for i in range(n)]
     long_listed = [(not err0[i]) and not banded[i] and in_tile[i] and w[i] > SW_SHORT_WMAX for i in range(n)]
     work = {2: 0, 3: 0, 7: sum(1 for c in cands if has_n[c["rid"]]), 17: sum(long_listed), 18: sum(strip_listed)}
