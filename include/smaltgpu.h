@@ -419,6 +419,36 @@ void smaltgpu_reads_free(smaltgpu_reads *rs);
 int smaltgpu_reads_parse(smaltgpu_reads *rs, const char *text, uint64_t len, int is_last, uint32_t max_reads, int nthreads,
                          smaltgpu_reads_view *view);
 
+/* ---- the same parse on the device (smg_reads_dev.hpp / smg_reads_dev.hip) -------------------------------------------------------
+ * smaltgpu_reads_parse_device copies `text[0..len)` to the device, finds the records of ALL candidate prompts at once (one
+ * speculative step of the reference's reader per prompt, the chain of records by pointer doubling, prefix sums, one output pass)
+ * and leaves the batch in HBM in the layout smaltgpu_map_batch_device and one side of smaltgpu_resident_reads take: d_read_off[0]
+ * is 0, d_quals is NULL without qualities.  Every rule is the one of smaltgpu_reads_parse for any shape of text (FASTA, wrapped
+ * lines, blank lines, stray '+' segments): the same reads, names, has_qual and consumed for the same is_last / max_reads, the same
+ * SMALTGPU_EFILE messages.  host_view (may be NULL: a caller who only maps and counts needs no host copy) is filled as
+ * smaltgpu_reads_parse fills it, by one copy of the compacted arrays and the names cut on the host; dev_view may be NULL too, not
+ * both.  The arrays of both views belong to the handle and hold until the next parse on it.  A handle serves one thread at a
+ * time; its work runs on a stream of its own and is complete when the call returns. */
+typedef struct smaltgpu_reads_dev smaltgpu_reads_dev;
+typedef struct smaltgpu_reads_device_view {
+  const uint8_t *d_bases, *d_quals;    /* device: total_bases bytes each; d_quals NULL without qualities */
+  const uint64_t *d_read_off;          /* device: nreads + 1 */
+  uint32_t nreads, has_qual;
+  uint64_t total_bases;
+  uint64_t consumed;                   /* as smaltgpu_reads_view.consumed */
+} smaltgpu_reads_device_view;
+smaltgpu_reads_dev *smaltgpu_reads_dev_create(int device);       /* NULL: no such device (smaltgpu_last_error) */
+void smaltgpu_reads_dev_free(smaltgpu_reads_dev *rd);
+int smaltgpu_reads_parse_device(smaltgpu_reads_dev *rd, const char *text, uint64_t len, int is_last, uint32_t max_reads,
+                                smaltgpu_reads_view *host_view, smaltgpu_reads_device_view *dev_view);
+/* For tests and measurements.  _configure: bytes of text per workgroup of the passes over the text (0: the default; a multiple of
+ * 64), a cap on the workgroups of the passes over the prompts (0: the default), and a number of bytes behind each array of the
+ * device view that the next parses fill with 0xA5 before they write.  _readback: array `which` (0 bases, 1 qualities, 2 offsets)
+ * of the last parse with the bytes behind it copied to dst (room for cap bytes); *nbytes: the array's own size; *launches (may be
+ * NULL): the kernel launches of the last parse. */
+int smaltgpu_reads_dev_configure(smaltgpu_reads_dev *rd, uint32_t block_bytes, uint32_t max_groups, uint32_t guard_bytes);
+int smaltgpu_reads_dev_readback(smaltgpu_reads_dev *rd, int which, void *dst, uint64_t cap, uint64_t *nbytes, uint32_t *launches);
+
 /* ---- reads from SAM and BAM files (smalt map -F sam|bam; host code, smg_alnin.hpp / smg_alnin.cpp) ------------------------------
  * The reference reads such files through the bambamc library when it is linked with it (infmt.c; smalt.c:584 opens the file,
  * :804-826 loads reads and mates of a template into the buffers, :1129-1184 sends a pair to rmapPair and anything else to

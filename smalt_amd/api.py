@@ -84,6 +84,11 @@ class ReadsView(C.Structure):          # smaltgpu_reads_view
                 ("read_off", C.POINTER(C.c_uint64)), ("names", C.POINTER(C.c_char)), ("name_off", C.POINTER(C.c_uint64)), ("consumed", C.c_uint64)]
 
 
+class ReadsDeviceView(C.Structure):    # smaltgpu_reads_device_view
+    _fields_ = [("d_bases", C.c_void_p), ("d_quals", C.c_void_p), ("d_read_off", C.c_void_p), ("nreads", C.c_uint32), ("has_qual", C.c_uint32),
+                ("total_bases", C.c_uint64), ("consumed", C.c_uint64)]
+
+
 IN_SAM, IN_BAM = 1, 2                  # smaltgpu_alnreads_create (smalt map -F sam | bam)
 
 
@@ -249,6 +254,12 @@ def lib():
         L.smaltgpu_reads_create.restype = C.c_void_p
         L.smaltgpu_reads_free.argtypes = [C.c_void_p]
         L.smaltgpu_reads_parse.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32, C.c_int, C.POINTER(ReadsView)]
+        L.smaltgpu_reads_dev_create.restype = C.c_void_p
+        L.smaltgpu_reads_dev_create.argtypes = [C.c_int]
+        L.smaltgpu_reads_dev_free.argtypes = [C.c_void_p]
+        L.smaltgpu_reads_parse_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(ReadsView), C.POINTER(ReadsDeviceView)]
+        L.smaltgpu_reads_dev_configure.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.smaltgpu_reads_dev_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.smaltgpu_map_split.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Params), C.c_void_p, C.c_int,
                                          C.POINTER(PostOut), C.POINTER(C.c_uint32)]
         L.smaltgpu_report_create.restype = C.c_void_p
@@ -423,6 +434,63 @@ class InsertHistogram:
     def close(self):
         if self.h:
             lib().smaltgpu_inshist_free(self.h)
+            self.h = None
+
+
+class ReadsDevice:
+    """FASTQ / FASTA text parsed on the device into a resident batch (smaltgpu_reads_parse_device): every rule is the one of the
+    host parser (smaltgpu_reads_parse), whatever the shape of the records."""
+
+    def __init__(self, device: int = 0):
+        self.h = C.c_void_p(lib().smaltgpu_reads_dev_create(device))
+        if not self.h:
+            raise SmaltGpuError(-1, lib().smaltgpu_last_error().decode())
+        self.raw = None
+
+    def configure(self, block_bytes: int = 0, max_groups: int = 0, guard_bytes: int = 0):
+        """tests and measurements: bytes of text per workgroup, a cap on the workgroups over the prompts, a guard behind the device arrays"""
+        _check(lib().smaltgpu_reads_dev_configure(self.h, block_bytes, max_groups, guard_bytes))
+        self.guard = guard_bytes
+
+    def parse_raw(self, data: bytes, is_last: bool = True, max_reads: int = 0, host: bool = True):
+        """-> (ReadsView or None, ReadsDeviceView); the arrays belong to the handle and hold until the next parse"""
+        hv, dv = ReadsView(), ReadsDeviceView()
+        _check(lib().smaltgpu_reads_parse_device(self.h, data, len(data), 1 if is_last else 0, max_reads, C.byref(hv) if host else None, C.byref(dv)))
+        self.raw = (hv if host else None, dv)
+        return self.raw
+
+    def parse(self, data: bytes, is_last: bool = True, max_reads: int = 0):
+        """-> (host, dev).  host: dict(names, reads, quals (None without qualities), read_off, has_qual, consumed) as the host parser
+        returns them.  dev: a ResidentReads whose side 0 is the batch in HBM (d_bases, d_quals, d_read_off, the offsets in host
+        memory, nreads), with .total_bases beside it: what map_batch_device and map_batch_ctx_resident take.  dev holds until the
+        next parse on this object."""
+        hv, dv = self.parse_raw(data, is_last, max_reads)
+        n = hv.nreads
+        off = [hv.read_off[i] for i in range(n + 1)]
+        bases = C.string_at(hv.bases, off[n]) if off[n] else b""
+        quals = C.string_at(hv.quals, off[n]) if (hv.has_qual and off[n]) else b""
+        names = C.string_at(hv.names, hv.name_off[n]).split(b"\0")[:-1] if n else []
+        host = dict(names=names, reads=[bases[off[i]:off[i + 1]] for i in range(n)], quals=[quals[off[i]:off[i + 1]] for i in range(n)] if hv.has_qual else None,
+                    read_off=off, has_qual=bool(hv.has_qual), consumed=int(hv.consumed))
+        dev = ResidentReads()
+        self._host_off = (C.c_uint64 * (n + 1))(*off)
+        dev.d_bases[0], dev.d_quals[0], dev.d_read_off[0] = dv.d_bases, dv.d_quals, dv.d_read_off
+        dev.read_off[0] = C.cast(self._host_off, C.c_void_p).value
+        dev.nreads[0] = n
+        dev.total_bases = int(dv.total_bases)
+        return host, dev
+
+    def readback(self, which: int):
+        """array `which` (0 bases, 1 qualities, 2 offsets) of the last parse as it lies in HBM -> (its bytes, the guard behind them, launches)"""
+        _, dv = self.raw
+        cap = (int(dv.total_bases) if which < 2 else (dv.nreads + 1) * 8) + getattr(self, "guard", 0) + 16
+        buf, n, launches = C.create_string_buffer(cap), C.c_uint64(), C.c_uint32()
+        _check(lib().smaltgpu_reads_dev_readback(self.h, which, buf, cap, C.byref(n), C.byref(launches)))
+        return buf.raw[:n.value], buf.raw[n.value:n.value + getattr(self, "guard", 0)], launches.value
+
+    def close(self):
+        if self.h:
+            lib().smaltgpu_reads_dev_free(self.h)
             self.h = None
 
 

@@ -48,6 +48,12 @@ const char VERSION[] = "0.2";
   exit(1);
 }
 
+// SMALTGPU_DEVICE_PARSE=1: FASTQ / FASTA text is parsed on the device (rd set; smaltgpu_reads_parse_device) and its host view is
+// used where the host parser's is otherwise: everything behind the parse is the same
+int parse_reads(smaltgpu_reads *rs, smaltgpu_reads_dev *rd, const char *text, uint64_t len, int is_last, uint32_t max_reads, int nthreads, smaltgpu_reads_view *v) {
+  return rd ? smaltgpu_reads_parse_device(rd, text, len, is_last, max_reads, v, nullptr) : smaltgpu_reads_parse(rs, text, len, is_last, max_reads, nthreads, v);
+}
+
 void usage() {
   fprintf(stderr,
           "usage: smaltgpu-map [options] <index prefix> <reads.fq|reads.fa>[.gz] [<mates.fq|mates.fa>[.gz]]\n"
@@ -84,6 +90,8 @@ void usage() {
           "  -I <file>  histogram of insert sizes written by `sample` (the reference's `smalt map -g <file>`; -g names the devices here):\n"
           "             it widens the insert range and weighs the pairings of a pair; its two prints go to standard output\n"
           "with two read files the reads are mapped as pairs (read i of the first with read i of the second file)\n"
+          "SMALTGPU_DEVICE_PARSE=1: FASTQ / FASTA text (not -F sam|bam) is parsed on the first device of -g, all records of a block at\n"
+          "once whatever their shape (FASTA, wrapped lines), instead of on the host threads; the output is the same\n"
           "\n"
           "usage: smaltgpu-map sample [-m <int>] [-n <int>] [-o <file>] [-q <int>] [-u <int>] [-B <int>] [-g <list>] <index prefix> <reads> <mates>\n"
           "  `smalt sample`: maps every <u>-th pair (default 100; every (pairs / 4098)-th when that is fewer) and writes the SAM lines\n"
@@ -128,6 +136,7 @@ struct Kept {
 struct Block {                                  // one block of reads (or pairs) on its way through the stages
   Kept kept[2];
   smaltgpu_reads *rs = nullptr, *rs2 = nullptr;
+  smaltgpu_reads_dev *rd = nullptr, *rd2 = nullptr;      // SMALTGPU_DEVICE_PARSE=1: the parsers on the device
   smaltgpu_reads_view v, v2;                    // v2: the mates
   smaltgpu_pairs *pairs = nullptr;
   int kind = 1;                                 // 1: single reads, 2: pairs (a run of a SAM / BAM file is of one kind)
@@ -306,6 +315,7 @@ int main(int argc, char **argv) {
   const bool serial_order = getenv("SMALTGPU_SERIAL_ORDER") && atoi(getenv("SMALTGPU_SERIAL_ORDER")) != 0;
   if (serial_order && alnfmt) die("SMALTGPU_SERIAL_ORDER=1 does not go with -F sam|bam: runs of pairs have no serial order of hit lists");
   if ((paired || alnfmt) && ins_min > ins_max) die("-j above -i");
+  const bool device_parse = !alnfmt && getenv("SMALTGPU_DEVICE_PARSE") && atoi(getenv("SMALTGPU_DEVICE_PARSE")) != 0;
   if (!strncmp(fmt, "bam", 3) && (!fmt[3] || fmt[3] == ':')) {                             // binary output: nothing else may go into it
     if (aliout) die("-a does not go with -f bam: a BAM file has no place for alignment blocks");
     if (histfil && !oufil) die("-I with -f bam needs -o <file>: the two histogram prints go to standard output");
@@ -366,19 +376,22 @@ int main(int argc, char **argv) {
       Source sc;
       sc.open(w ? matefil : readfil);
       smaltgpu_reads *rs = smaltgpu_reads_create();
+      smaltgpu_reads_dev *rd = device_parse ? smaltgpu_reads_dev_create(devices.empty() ? 0 : devices[0]) : nullptr;
+      if (device_parse && !rd) die("cannot parse the reads on the device", smaltgpu_last_error());
       uint64_t win = 1u << 24;
       for (;;) {
         uint64_t got = 0; bool last = false;
         const char *text = sc.window(win, &got, &last);
         if (!got) break;
         smaltgpu_reads_view v;
-        if (smaltgpu_reads_parse(rs, text, got, last ? 1 : 0, 0, nthreads, &v)) die("cannot parse the reads", smaltgpu_last_error());
+        if (parse_reads(rs, rd, text, got, last ? 1 : 0, 0, nthreads, &v)) die("cannot parse the reads", smaltgpu_last_error());
         if (!v.nreads && !last) { win *= 4; continue; }
         count[w] += v.nreads;
         sc.consume(v.consumed);
         if (last) break;
       }
       smaltgpu_reads_free(rs);
+      smaltgpu_reads_dev_free(rd);
       sc.close();
     }
     if (count[0] != count[1]) die("the two read files hold different numbers of reads");
@@ -476,6 +489,12 @@ int main(int argc, char **argv) {
   const int NWORK = per_dev * ndev, NBLK = NWORK + 2;
   std::vector<Block> blk((size_t)NBLK);
   for (Block &b : blk) { b.rs = smaltgpu_reads_create(); b.kind = paired ? 2 : 1; if (paired) { b.rs2 = smaltgpu_reads_create(); b.pairs = smaltgpu_pairs_create(); } }
+  if (device_parse)
+    for (Block &b : blk) {
+      b.rd = smaltgpu_reads_dev_create(devices[0]);
+      if (paired) b.rd2 = smaltgpu_reads_dev_create(devices[0]);
+      if (!b.rd || (paired && !b.rd2)) die("cannot parse the reads on the device", smaltgpu_last_error());
+    }
   smaltgpu_alnreads *aln = alnfmt ? smaltgpu_alnreads_create(alnfmt) : nullptr;            // owned by the parser thread until it is joined
   if (alnfmt && !aln) die("input", smaltgpu_last_error());
   // a failing call's text, never empty (the block must not pass for mapped when a call failed without a message)
@@ -499,14 +518,14 @@ int main(int argc, char **argv) {
       uint64_t win = bytes_per_read > 0 ? (uint64_t)(bytes_per_read * (double)batch * 1.05) + 65536 : (1u << 20);
       const double tp0 = now();
       // up to `want` reads from a source; exact: the block must hold exactly that many unless the source ends (the mates of a block)
-      auto parse_from = [&](Source &sc, smaltgpu_reads *rs, smaltgpu_reads_view *v, uint32_t want, bool exact) -> bool {
+      auto parse_from = [&](Source &sc, smaltgpu_reads *rs, smaltgpu_reads_dev *rd, smaltgpu_reads_view *v, uint32_t want, bool exact) -> bool {
         bool last = false;
         uint64_t w = win;
         for (;;) {
           uint64_t got = 0;
           const char *text = sc.window(w, &got, &last);
           if (!got) { v->nreads = 0; return true; }
-          if (smaltgpu_reads_parse(rs, text, got, last ? 1 : 0, want, nthreads, v)) {
+          if (parse_reads(rs, rd, text, got, last ? 1 : 0, want, nthreads, v)) {
             std::lock_guard<std::mutex> lk(mu); b.err = why("cannot parse the reads"); failed = true; cv.notify_all(); return false;
           }
           if (last || (exact ? v->nreads == want : v->nreads > 0)) return true;
@@ -540,8 +559,8 @@ int main(int argc, char **argv) {
         // stretches of the input are parsed until a block of sampled pairs is full: pair i is kept when i % interval == 0 (smalt.c:809-818)
         b.kept[0].clear(); b.kept[1].clear();
         for (;;) {
-          if (!parse_from(src, b.rs, &b.v, (uint32_t)batch, false)) return;
-          if (!parse_from(src2, b.rs2, &b.v2, b.v.nreads ? b.v.nreads : 1, true)) return;
+          if (!parse_from(src, b.rs, b.rd, &b.v, (uint32_t)batch, false)) return;
+          if (!parse_from(src2, b.rs2, b.rd2, &b.v2, b.v.nreads ? b.v.nreads : 1, true)) return;
           if (b.v2.nreads != b.v.nreads) { std::lock_guard<std::mutex> lk(mu); b.err = "the two read files hold different numbers of reads"; failed = true; cv.notify_all(); return; }
           if (!b.v.nreads) break;
           for (uint32_t i = 0; i < b.v.nreads; i++)
@@ -554,10 +573,10 @@ int main(int argc, char **argv) {
           if (b.kept[0].read_off.size() - 1 + (uint64_t)batch / interval >= (uint64_t)batch) break;      // another stretch would not fit
         }
         b.kept[0].view(&b.v); b.kept[1].view(&b.v2);
-      } else if (!parse_from(src, b.rs, &b.v, (uint32_t)batch, false)) return;
+      } else if (!parse_from(src, b.rs, b.rd, &b.v, (uint32_t)batch, false)) return;
       if (sampling || aln) {                               // both sides are there
       } else if (paired && b.v.nreads) {
-        if (!parse_from(src2, b.rs2, &b.v2, b.v.nreads, true)) return;
+        if (!parse_from(src2, b.rs2, b.rd2, &b.v2, b.v.nreads, true)) return;
         if (b.v2.nreads != b.v.nreads) { std::lock_guard<std::mutex> lk(mu); b.err = "the two read files hold different numbers of reads"; failed = true; cv.notify_all(); return; }
       } else if (paired) {
         bool last2 = false; uint64_t got2 = 0;
@@ -677,7 +696,7 @@ int main(int argc, char **argv) {
   for (std::thread &t : workers) t.join();
   if (failed && failure.empty()) for (Block &x : blk) if (!x.err.empty()) failure = x.err;
   for (Worker &W : wk) { if (W.mp) smaltgpu_mapper_free(W.mp); if (W.post) smaltgpu_post_free(W.post); }
-  for (Block &b : blk) { smaltgpu_reads_free(b.rs); if (b.rs2) smaltgpu_reads_free(b.rs2); if (b.pairs) smaltgpu_pairs_free(b.pairs); }
+  for (Block &b : blk) { smaltgpu_reads_dev_free(b.rd); smaltgpu_reads_dev_free(b.rd2); smaltgpu_reads_free(b.rs); if (b.rs2) smaltgpu_reads_free(b.rs2); if (b.pairs) smaltgpu_pairs_free(b.pairs); }
   double aln_s[3] = {0, 0, 0};
   if (aln) smaltgpu_alnreads_times(aln, &aln_s[0], &aln_s[1], &aln_s[2]);
   smaltgpu_alnreads_free(aln);
@@ -713,8 +732,8 @@ int main(int argc, char **argv) {
             tm > 0 ? (double)nreads_total / tm : 0.0);
     double tc = 0, tm_ = 0, tp = 0;
     for (int w = 0; w < NWORK; w++) { tc += t_create[w]; tm_ += t_map[w]; tp += t_post[w]; }
-    fprintf(stderr, "smaltgpu-map: stages [s]: parse %.3f | %d workers on %d device(s), mean per worker: mapper set-up %.3f  map %.3f  post %.3f | wait %.3f emit %.3f write %.3f\n",
-            t_parse, NWORK, ndev, tc / NWORK, tm_ / NWORK, tp / NWORK, t_wait, t_emit, t_write);
+    fprintf(stderr, "smaltgpu-map: stages [s]: parse%s %.3f | %d workers on %d device(s), mean per worker: mapper set-up %.3f  map %.3f  post %.3f | wait %.3f emit %.3f write %.3f\n",
+            device_parse ? " (on the device)" : "", t_parse, NWORK, ndev, tc / NWORK, tm_ / NWORK, tp / NWORK, t_wait, t_emit, t_write);
     if (alnfmt) fprintf(stderr, "smaltgpu-map: of parse [s]: inflate %.3f  decode and collate %.3f  runs copied out %.3f (the rest: copies into the blocks, page faults of the input)\n",
                         aln_s[0], aln_s[1], aln_s[2]);
   }

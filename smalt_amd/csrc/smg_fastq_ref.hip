@@ -20,37 +20,6 @@ namespace smg {
 
 #define FQ_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #x, hipGetErrorString(e_)); goto fail; } } while (0)
 
-// the lane's bytes of the tile that starts at t0: text[o, o + n), n <= 16, and the byte in front of them (0: none).  The text buffer
-// is padded to a multiple of FA_TILE behind `len`, and o is a multiple of 16, so the load stays inside the allocation.
-__device__ inline uint32_t fq_lane_load(const uint8_t *text, uint64_t t0, uint64_t end, uint64_t *o_out, uint8_t (&c)[FA_LANE_BYTES], uint8_t *prev) {
-  const uint64_t o = t0 + (uint64_t)threadIdx.x * FA_LANE_BYTES;
-  *o_out = o;
-  *prev = 0;
-  if (o >= end) return 0;
-  const uint4 v = *reinterpret_cast<const uint4 *>(text + o);
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (uint32_t i = 0; i < FA_LANE_BYTES; i++) c[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-  if (o > 0) *prev = text[o - 1];
-  return end - o < FA_LANE_BYTES ? (uint32_t)(end - o) : FA_LANE_BYTES;
-}
-
-// exclusive sum of v over the workgroup (256 threads); *total: the sum.  wsum: 4 words of LDS
-__device__ inline uint32_t fq_block_scan_sum(uint32_t v, uint32_t *wsum, uint32_t *total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t s = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(s, d); if (lane >= d) s += o; }
-  __syncthreads();                       // the last use of wsum is over
-  if (lane == 63) wsum[wave] = s;
-  __syncthreads();
-  uint32_t pre = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < 4; w++) { if (w == wave) pre = all; all += wsum[w]; }
-  *total = all;
-  return pre + s - v;
-}
-
 // blk_nb[b], blk_cd[b]: the counts of block b (a tile holds at most 4096 non-blank bytes and 2048 candidates: 16 bits each)
 __global__ void __launch_bounds__(256) k_fq_count(const uint8_t *text, uint64_t len, uint32_t block_bytes, uint32_t *gran_nb, uint64_t *blk_nb, uint64_t *blk_cd) {
   __shared__ uint32_t wsum[4];
@@ -106,6 +75,21 @@ __global__ void __launch_bounds__(256) k_fq_cands(const uint8_t *text, uint64_t 
     }
     at += tot;
   }
+}
+
+// the three launches in front of a walk, for the readers of other files (smg_reads_dev.hip): what fastq_ref_parse_device launches itself
+hipError_t fq_launch_counts(hipStream_t st, const uint8_t *text, uint64_t len, uint32_t block_bytes, uint64_t nblk, uint32_t *gran_nb, uint64_t *blk_nb, uint64_t *blk_cd) {
+  hipLaunchKernelGGL(k_fq_count, dim3((unsigned)nblk), dim3(256), 0, st, text, len, block_bytes, gran_nb, blk_nb, blk_cd);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : fq_launch_scan(st, blk_nb, blk_cd, nblk);
+}
+hipError_t fq_launch_scan(hipStream_t st, uint64_t *a, uint64_t *b, uint64_t n) {
+  hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(256), 0, st, a, b, n);
+  return hipGetLastError();
+}
+hipError_t fq_launch_cands(hipStream_t st, const uint8_t *text, uint64_t len, uint32_t block_bytes, uint64_t nblk, const uint64_t *blk_cd, uint64_t *cand, uint64_t ncand) {
+  hipLaunchKernelGGL(k_fq_cands, dim3((unsigned)nblk), dim3(256), 0, st, text, len, block_bytes, blk_cd, cand, ncand);
+  return hipGetLastError();
 }
 
 __global__ void __launch_bounds__(64) k_fq_walk(FqText t, FqRecord *rec, uint64_t cap, FqWalk *out) {
