@@ -146,15 +146,15 @@ extern "C" int smaltgpu_index_build_device(smaltgpu_index **out, int device, con
   smaltgpu_index_desc ds;
   memset(&ds, 0, sizeof(ds));
   ds.k = k; ds.s = s; ds.typ = b.typ; ds.nbits_key = b.nbits_key; ds.nbits_lo = b.nbits_lo; ds.npos = b.npos; ds.nwords = b.nwords;
-  ds.idx = b.idx; ds.pos = b.pos; ds.wordidx = b.wordidx; ds.posidx = b.posidx; ds.nseq = nseq; ds.sop = seq_off; ds.packed = b.packed; ds.on_device = 1;
+  uint32_t *const posidx = b.posidx;
+  ds.idx = b.idx; ds.pos = b.pos; ds.wordidx = b.wordidx; ds.posidx = posidx; ds.nseq = nseq; ds.sop = seq_off; ds.packed = b.packed; ds.on_device = 1;
   smaltgpu_index *ix = nullptr;
-  const int rv = smaltgpu_index_create(&ix, &ds, device);
-  if (rv) { (void)hipFree(b.idx); (void)hipFree(b.pos); (void)hipFree(b.wordidx); (void)hipFree(b.posidx); (void)hipFree(b.packed); return rv; }
-  void *own[5] = {b.idx, b.pos, b.wordidx, b.posidx, b.packed};      // adopted: freed with the index
-  for (void *p : own) if (p && ix->nbufs < 8) ix->bufs[ix->nbufs++] = p;
+  TRY(smaltgpu_index_create(&ix, &ds, device));                        // refused: the arrays go with b
+  // adopted: freed with the index (two of its eight places hold the offsets it uploaded itself)
+  for (DevMem<uint32_t> *m : {&b.idx, &b.pos, &b.wordidx, &b.posidx, &b.packed}) if (*m) ix->bufs[ix->nbufs++] = m->release();
   // The reference's reader takes only 2 * nwords + 1 of the collision words (hashidx.c:1257; smg_indexfile.hpp), so a loaded
   // index runs with posidx[nwords] == 0; the built image must behave the same.  smaltgpu_index_save writes npos there.
-  if (b.typ != IDX_PERFECT && b.posidx) HIPCHK(hipMemset(b.posidx + b.nwords, 0, 4));
+  if (b.typ != IDX_PERFECT && posidx) HIPCHK(hipMemset(posidx + b.nwords, 0, 4));
   ix->maxpos = b.maxpos; ix->built = true;
   for (int64_t i = 0; i < nseq; i++) ix->names.emplace_back(names[i] ? names[i] : "");
   if (build_ms) *build_ms = b.build_ms;
@@ -176,7 +176,7 @@ extern "C" int smaltgpu_index_build(smaltgpu_index **out, int device, const uint
 }
 
 // ---- the same from the text of a FASTA file, parsed on the device (smg_fasta.hip) ----
-// bases in HBM (p->d_bases, the caller's), offsets, and the names cleaned on the host from the header lines the device found
+// bases in HBM (p->d_bases, which goes with p), offsets, and the names cleaned on the host from the header lines the device found
 static int parse_fasta_text(int device, const char *text, uint64_t text_len, uint32_t flags, FastaParsed *p, std::vector<std::string> *names) {
   if (!text && text_len) return fail(SMALTGPU_EARG, "null argument");
   if (flags & ~(uint32_t)SMALTGPU_TEXT_FASTQ) return fail(SMALTGPU_EARG, "unknown flags %#x", flags);
@@ -188,13 +188,11 @@ static int parse_fasta_text(int device, const char *text, uint64_t text_len, uin
   while (first < text_len && fa_isspace((uint8_t)text[first])) first++;
   if (p->keep_fastq_text && first < text_len && (text[first] == '@' || text[first] == '+')) {
     // the first prompt already says so: the FASTA route would refuse the text in its output pass, so it is not tried
-    if (fastq_ref_parse_device(text, text_len, block, nullptr, p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
+    if (fastq_ref_parse_device(text, text_len, block, p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
   } else if (fasta_parse_device(text, text_len, block, p, err, sizeof(err))) {
     // a text with '@' or '+' prompts: the FASTA route has found that out and left the text in HBM; the records are walked instead
     if (!p->d_text) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
-    uint8_t *d_text = p->d_text;
-    p->d_text = nullptr;
-    if (fastq_ref_parse_device(text, text_len, block, d_text, p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
+    if (fastq_ref_parse_device(text, text_len, block, p, err, sizeof(err))) return fail(SMALTGPU_EARG, "cannot read the reference sequences: %s", err);
   }
   names->clear();
   for (const uint64_t o : p->hdr_text_off) names->push_back(fa_clean_name(text + o + 1, (size_t)(text_len - o - 1)));
@@ -211,7 +209,6 @@ extern "C" int smaltgpu_index_build_text_ex(smaltgpu_index **out, int device, co
   std::vector<const char *> ptrs;
   for (const std::string &x : names) ptrs.push_back(x.c_str());
   rv = smaltgpu_index_build_device(out, device, p.d_bases, p.seq_off.data(), ptrs.data(), (int64_t)names.size(), k, s, build_ms);
-  (void)hipFree(p.d_bases);
   if (!rv && parse_ms) *parse_ms = p.pass_a_ms + p.compose_ms + p.pass_b_ms;
   return rv;
 }
@@ -236,7 +233,6 @@ extern "C" int smaltgpu_fasta_parse_ex(smaltgpu_fasta **out, int device, const c
   if (!rv) {
     fa->bases.resize((size_t)p.nbases + 1);
     if (p.nbases && hipMemcpy(fa->bases.data(), p.d_bases, p.nbases, hipMemcpyDeviceToHost) != hipSuccess) rv = fail(SMALTGPU_ENODEV, "copy of the parsed sequences to the host failed");
-    (void)hipFree(p.d_bases);
   }
   if (rv) { delete fa; return rv; }
   fa->seq_off.swap(p.seq_off);

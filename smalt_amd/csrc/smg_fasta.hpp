@@ -21,6 +21,9 @@
 #include <string>
 #include <vector>
 #include "smg_common.h"
+#if defined(__HIPCC__)
+#include "smg_devmem.hpp"
+#endif
 
 namespace smg {
 
@@ -115,18 +118,20 @@ inline uint32_t fa_block_bytes(const char *env) {       // SMALTGPU_FASTA_BLOCK:
   return (uint32_t)(v < FA_BLOCK_MIN ? FA_BLOCK_MIN : v > FA_BLOCK_MAX ? FA_BLOCK_MAX : v);
 }
 
-// The parse on the device (smg_fasta.hip).  text: host memory.  d_bases (hipMalloc, owned by the caller) receives the bases;
+#if defined(__HIPCC__)
+// The parse on the device (smg_fasta.hip).  text: host memory.  d_bases receives the bases and goes with the FastaParsed;
 // seq_off gets nseq + 1 entries; hdr_text_off the offset of each header's prompt in the text.  block_bytes: fa_block_bytes().
 struct FastaParsed {
-  uint8_t *d_bases = nullptr;
+  DevMem<uint8_t> d_bases;
   uint64_t nbases = 0;
   std::vector<uint64_t> seq_off, hdr_text_off;
   float upload_ms = 0, pass_a_ms = 0, compose_ms = 0, pass_b_ms = 0;
-  // in: a text refused for its '@' / '+' prompts is left in HBM (d_text, padded to a multiple of FA_TILE; the caller's) for the
-  // reader of smg_fastq_ref.hpp
+  // in: a text refused for its '@' / '+' prompts is left in HBM (d_text, padded to a multiple of FA_TILE) for the reader of
+  // smg_fastq_ref.hpp, which takes it from here
   bool keep_fastq_text = false;
-  uint8_t *d_text = nullptr;
+  DevMem<uint8_t> d_text;
 };
 int fasta_parse_device(const char *text, uint64_t text_len, uint32_t block_bytes, FastaParsed *out, char *err, size_t errlen);
+#endif
 
 }  // namespace smg

@@ -196,43 +196,11 @@ inline std::string fq_refusal(const FqWalk &w, const char *text, uint64_t text_l
   return std::string();
 }
 
-// The parse on the device (smg_fastq_ref.hip), with the results of fasta_parse_device.  d_text: the text already in HBM, padded to
-// a multiple of FA_TILE (nullptr: it is copied there); freed here.  pass_a_ms: candidates and prefix counts (three launches),
-// compose_ms: the walk, pass_b_ms: the output pass.
-int fastq_ref_parse_device(const char *text, uint64_t text_len, uint32_t block_bytes, uint8_t *d_text, FastaParsed *out, char *err, size_t errlen);
-
 #if defined(__HIPCC__)
-// ---- device side, shared by the kernels of smg_fastq_ref.hip and smg_reads_dev.hip --------------------------------------------
-// the lane's bytes of the tile that starts at t0: text[o, o + n), n <= 16, and the byte in front of them (0: none).  The text buffer
-// is padded to a multiple of FA_TILE behind `len`, and o is a multiple of 16, so the load stays inside the allocation.
-__device__ inline uint32_t fq_lane_load(const uint8_t *text, uint64_t t0, uint64_t end, uint64_t *o_out, uint8_t (&c)[FA_LANE_BYTES], uint8_t *prev) {
-  const uint64_t o = t0 + (uint64_t)threadIdx.x * FA_LANE_BYTES;
-  *o_out = o;
-  *prev = 0;
-  if (o >= end) return 0;
-  const uint4 v = *reinterpret_cast<const uint4 *>(text + o);
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (uint32_t i = 0; i < FA_LANE_BYTES; i++) c[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-  if (o > 0) *prev = text[o - 1];
-  return end - o < FA_LANE_BYTES ? (uint32_t)(end - o) : FA_LANE_BYTES;
-}
-
-// exclusive sum of v over the workgroup (256 threads); *total: the sum.  wsum: 4 words of LDS
-__device__ inline uint32_t fq_block_scan_sum(uint32_t v, uint32_t *wsum, uint32_t *total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t s = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(s, d); if (lane >= d) s += o; }
-  __syncthreads();                       // the last use of wsum is over
-  if (lane == 63) wsum[wave] = s;
-  __syncthreads();
-  uint32_t pre = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < 4; w++) { if (w == wave) pre = all; all += wsum[w]; }
-  *total = all;
-  return pre + s - v;
-}
+// The parse on the device (smg_fastq_ref.hip), with the results of fasta_parse_device.  The text in HBM is out->d_text where
+// fasta_parse_device has left it there (it is taken from there and gone when the call returns), otherwise it is copied there.
+// pass_a_ms: candidates and prefix counts (three launches), compose_ms: the walk, pass_b_ms: the output pass.
+int fastq_ref_parse_device(const char *text, uint64_t text_len, uint32_t block_bytes, FastaParsed *out, char *err, size_t errlen);
 
 // launchers of k_fq_count + k_fq_scan, of k_fq_scan alone (a and b: n + 1 entries) and of k_fq_cands (smg_fastq_ref.hip)
 hipError_t fq_launch_counts(hipStream_t st, const uint8_t *text, uint64_t len, uint32_t block_bytes, uint64_t nblk, uint32_t *gran_nb, uint64_t *blk_nb, uint64_t *blk_cd);

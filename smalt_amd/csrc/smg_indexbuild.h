@@ -2,15 +2,11 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include "smg_devmem.hpp"
+#endif
 
 namespace smg {
-
-struct BuiltIndex {                 // device arrays (hipMalloc), owned by the caller
-  int typ, nbits_key, nbits_lo;
-  uint32_t nkeys, npos, nwords, maxpos;
-  uint32_t *idx, *pos, *wordidx, *posidx, *packed;
-  float build_ms;                   // device time of the whole construction (HIP events)
-};
 
 // selectHashTyp (smalt.c:268-332): 0 or -1 (unsupported)
 int index_geometry(int k, int s, uint64_t totlen, int *typ, int *nbits_key, int *nbits_lo);
@@ -41,7 +37,16 @@ inline int64_t index_carry(const uint64_t *sop, int64_t nseq, int k, int s, uint
   return -1;
 }
 
+#if defined(__HIPCC__)
+struct BuiltIndex {                 // the device arrays go with it, or are released to whoever keeps the index
+  int typ = 0, nbits_key = 0, nbits_lo = 0;
+  uint32_t nkeys = 0, npos = 0, nwords = 0, maxpos = 0;
+  DevMem<uint32_t> idx, pos, wordidx, posidx, packed;
+  float build_ms = 0;               // device time of the whole construction (HIP events)
+};
+
 // d_ascii: the concatenated reference sequences in HBM (tot bytes, letters as in FASTA); h_sop: nseq + 1 offsets (host)
 int build_index_device(const uint8_t *d_ascii, uint64_t tot, const uint64_t *h_sop, int nseq, int k, int s, BuiltIndex *out, char *err, size_t errlen);
+#endif
 
 }  // namespace smg

@@ -18,15 +18,12 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 #include "smg_common.h"
 #include "smg_indexbuild.h"
 
 namespace smg {
-
-#define IB_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #x, hipGetErrorString(e_)); goto fail; } } while (0)
 
 // sequence.c:287-322: upper-case; U -> T; A C G T -> 0..3; everything else -> 5
 __device__ inline uint8_t ref_code_of_ascii(uint8_t c) {
@@ -194,129 +191,102 @@ int index_geometry(int k, int s, uint64_t totlen, int *typ, int *nbits_key, int 
 
 int build_index_device(const uint8_t *d_ascii, uint64_t tot, const uint64_t *h_sop, int nseq, int k, int s, BuiltIndex *out, char *err, size_t errlen) {
   BuiltIndex b;
-  memset(&b, 0, sizeof(b));
-  uint64_t *d_sop = nullptr, *key64 = nullptr, *okey = nullptr, *skey = nullptr;
-  uint32_t *flag = nullptr, *slot = nullptr, *opos = nullptr, *head = nullptr, *key32 = nullptr, *skey32 = nullptr;
-  unsigned long long *d_nvalid = nullptr, h_nvalid = 0;
-  void *tmp = nullptr;
-  size_t tmp_bytes = 0, need = 0;
-  uint32_t last_slot = 0, last_flag = 0;
-  uint64_t n = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   if (index_geometry(k, s, tot, &b.typ, &b.nbits_key, &b.nbits_lo) || b.nbits_key > 31 || nseq < 1 || s > 200) { snprintf(err, errlen, "unsupported index geometry (k=%d s=%d)", k, s); return -1; }
   for (int i = 0; i < nseq; i++) if (h_sop[i + 1] - h_sop[i] < (uint64_t)k) { snprintf(err, errlen, "sequence %d is shorter than the word length (hashidx.c:499)", i); return -1; }
-  {                                                                        // the reference's walk over the lengths: refusal and maxpos (only s > k leaves the grid)
-    const int64_t bad = index_carry(h_sop, nseq, k, s, &b.maxpos);         // hashidx.c:992
-    if (bad >= 0) {
-      snprintf(err, errlen, "the reference refuses sampling step %d with word length %d for sequence %lld: the one in front of it ends too far before the next sampled word (hashidx.c:494)",
-               s, k, (long long)bad);
-      return -1;
-    }
+  const int64_t bad = index_carry(h_sop, nseq, k, s, &b.maxpos);         // the reference's walk over the lengths: refusal and maxpos (hashidx.c:992)
+  if (bad >= 0) {
+    snprintf(err, errlen, "the reference refuses sampling step %d with word length %d for sequence %lld: the one in front of it ends too far before the next sampled word (hashidx.c:494)",
+             s, k, (long long)bad);
+    return -1;
   }
-  {
   const unsigned cap = ib_grid_cap(getenv("SMALTGPU_INDEX_GRID"));      // read once per build
   b.nkeys = 1u << b.nbits_key;
   const uint64_t ntup = (tot + (uint64_t)s - 1) / (uint64_t)s;           // serials 0 .. ntup-1 start inside the reference
   const uint64_t nwords = tot / 10 + 1;
   const bool k32 = b.typ == IDX_PERFECT && 2 * k <= 30;                  // 32-bit keys with a sentinel behind the largest word
-#define IB_TMP(call_null, call_real) { IB_HIP(call_null); if (need > tmp_bytes) { if (tmp) IB_HIP(hipFree(tmp)); tmp = nullptr; tmp_bytes = need; IB_HIP(hipMalloc(&tmp, tmp_bytes)); } IB_HIP(call_real); }
-  IB_HIP(hipEventCreate(&e0)); IB_HIP(hipEventCreate(&e1));
-  IB_HIP(hipMalloc((void **)&d_sop, ((size_t)nseq + 1) * 8));
-  IB_HIP(hipMemcpy(d_sop, h_sop, ((size_t)nseq + 1) * 8, hipMemcpyHostToDevice));
-  IB_HIP(hipMalloc((void **)&b.packed, nwords * 4));
-  IB_HIP(hipMalloc((void **)&b.idx, ((size_t)b.nkeys + 2) * 4));
-  IB_HIP(hipMalloc((void **)&d_nvalid, 8));
+  // scratch: it goes with this scope on every return, and so do the arrays of b until they are moved out
+  DevMem<uint64_t> sop, key64, okey, skey; DevMem<uint32_t> flag, slot, opos, head, key32, skey32; DevMem<unsigned long long> nvalid; DevMem<char> tmp;
+  DevEvent e0, e1;
+  size_t need = 0;                                                     // bytes of temporary storage a rocPRIM call asks for
+  uint64_t n = 0;                                                      // indexed serials
+  // a rocPRIM call: once for the bytes of temporary storage it needs, once for the work
+#define IB_TMP(call_null, call_real) { SMG_HIP(call_null); if (need > tmp.bytes()) SMG_HIP(tmp.alloc(need)); SMG_HIP(call_real); }
+  SMG_HIP(e0.create()); SMG_HIP(e1.create());
+  SMG_HIP(sop.alloc((size_t)nseq + 1));
+  SMG_HIP(hipMemcpy(sop, h_sop, ((size_t)nseq + 1) * 8, hipMemcpyHostToDevice));
+  SMG_HIP(b.packed.alloc(nwords));
+  SMG_HIP(b.idx.alloc((size_t)b.nkeys + 2));
+  SMG_HIP(nvalid.alloc(1));
   if (k32) {
-    IB_HIP(hipMalloc((void **)&key32, (ntup + 1) * 4));
-    IB_HIP(hipMalloc((void **)&skey32, (ntup + 1) * 4));
-    IB_HIP(hipMalloc((void **)&opos, (ntup + 1) * 4));
-    IB_HIP(hipMalloc((void **)&b.pos, (ntup + 1) * 4));
+    SMG_HIP(key32.alloc(ntup + 1)); SMG_HIP(skey32.alloc(ntup + 1));
+    SMG_HIP(opos.alloc(ntup + 1)); SMG_HIP(b.pos.alloc(ntup + 1));
   } else {
-    IB_HIP(hipMalloc((void **)&flag, (ntup + 1) * 4));
-    IB_HIP(hipMalloc((void **)&slot, (ntup + 1) * 4));
-    IB_HIP(hipMalloc((void **)&key64, (ntup + 1) * 8));
+    SMG_HIP(flag.alloc(ntup + 1)); SMG_HIP(slot.alloc(ntup + 1));
+    SMG_HIP(key64.alloc(ntup + 1));
   }
-  IB_HIP(hipEventRecord(e0, 0));
-  IB_HIP(hipMemsetAsync(d_nvalid, 0, 8, 0));
-  IB_HIP(hipMemsetAsync(b.idx, 0, ((size_t)b.nkeys + 2) * 4, 0));
-  hipLaunchKernelGGL(k_ib_pack, dim3(ib_grid(nwords, cap)), dim3(256), 0, 0, d_ascii, tot, nwords, b.packed);
+  SMG_HIP(hipEventRecord(e0, 0));
+  SMG_HIP(hipMemsetAsync(nvalid, 0, 8, 0));
+  SMG_HIP(hipMemsetAsync(b.idx, 0, ((size_t)b.nkeys + 2) * 4, 0));
+  hipLaunchKernelGGL(k_ib_pack, dim3(ib_grid(nwords, cap)), dim3(256), 0, 0, d_ascii, tot, nwords, b.packed.get());
   if (k32) {
-    hipLaunchKernelGGL(k_ib_kmers<true>, dim3(ib_grid(ntup, cap)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, d_sop, nseq, ntup, k, s, b.nbits_key, b.nbits_lo,
-                       (uint32_t *)nullptr, (uint64_t *)nullptr, key32, opos, d_nvalid);
-    IB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ib_kmers<true>, dim3(ib_grid(ntup, cap)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, sop.get(), nseq, ntup, k, s, b.nbits_key, b.nbits_lo,
+                       (uint32_t *)nullptr, (uint64_t *)nullptr, key32.get(), opos.get(), nvalid.get());
+    SMG_HIP(hipGetLastError());
     // stable sort by key: serials of equal keys stay ascending, serials that are not indexed end up behind
-    IB_TMP(rocprim::radix_sort_pairs(nullptr, need, key32, skey32, opos, b.pos, (size_t)ntup, 0u, (unsigned)(2 * k + 1), 0),
-           rocprim::radix_sort_pairs(tmp, need, key32, skey32, opos, b.pos, (size_t)ntup, 0u, (unsigned)(2 * k + 1), 0));
-    IB_HIP(hipMemcpy(&h_nvalid, d_nvalid, 8, hipMemcpyDeviceToHost));
+    IB_TMP(rocprim::radix_sort_pairs(nullptr, need, key32.get(), skey32.get(), opos.get(), b.pos.get(), (size_t)ntup, 0u, (unsigned)(2 * k + 1), 0),
+           rocprim::radix_sort_pairs(tmp.get(), need, key32.get(), skey32.get(), opos.get(), b.pos.get(), (size_t)ntup, 0u, (unsigned)(2 * k + 1), 0));
+    unsigned long long h_nvalid = 0;
+    SMG_HIP(hipMemcpy(&h_nvalid, nvalid, 8, hipMemcpyDeviceToHost));
     n = h_nvalid;
     b.npos = (uint32_t)n;
-    hipLaunchKernelGGL(k_ib_runend32, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey32, n, b.idx);
-    IB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ib_runend32, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey32.get(), n, b.idx.get());
+    SMG_HIP(hipGetLastError());
   } else {
-    hipLaunchKernelGGL(k_ib_kmers<false>, dim3(ib_grid(ntup, cap)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, d_sop, nseq, ntup, k, s, b.nbits_key, b.nbits_lo,
-                       flag, key64, (uint32_t *)nullptr, (uint32_t *)nullptr, d_nvalid);
-    IB_HIP(hipGetLastError());
+    uint32_t last_slot = 0, last_flag = 0, lh = 0, ls = 0;
+    hipLaunchKernelGGL(k_ib_kmers<false>, dim3(ib_grid(ntup, cap)), dim3(256), (size_t)(256 * s + k + 16), 0, d_ascii, sop.get(), nseq, ntup, k, s, b.nbits_key, b.nbits_lo,
+                       flag.get(), key64.get(), (uint32_t *)nullptr, (uint32_t *)nullptr, nvalid.get());
+    SMG_HIP(hipGetLastError());
     // ordered compaction of the indexed serials
-    IB_TMP(rocprim::exclusive_scan(nullptr, need, flag, slot, 0u, (size_t)ntup, rocprim::plus<uint32_t>(), 0),
-           rocprim::exclusive_scan(tmp, need, flag, slot, 0u, (size_t)ntup, rocprim::plus<uint32_t>(), 0));
+    IB_TMP(rocprim::exclusive_scan(nullptr, need, flag.get(), slot.get(), 0u, (size_t)ntup, rocprim::plus<uint32_t>(), 0),
+           rocprim::exclusive_scan(tmp.get(), need, flag.get(), slot.get(), 0u, (size_t)ntup, rocprim::plus<uint32_t>(), 0));
     if (ntup) {
-      IB_HIP(hipMemcpy(&last_slot, slot + (ntup - 1), 4, hipMemcpyDeviceToHost));
-      IB_HIP(hipMemcpy(&last_flag, flag + (ntup - 1), 4, hipMemcpyDeviceToHost));
+      SMG_HIP(hipMemcpy(&last_slot, slot + (ntup - 1), 4, hipMemcpyDeviceToHost));
+      SMG_HIP(hipMemcpy(&last_flag, flag + (ntup - 1), 4, hipMemcpyDeviceToHost));
     }
     n = (uint64_t)last_slot + last_flag;
     b.npos = (uint32_t)n;
-    IB_HIP(hipMalloc((void **)&okey, (n + 1) * 8));
-    IB_HIP(hipMalloc((void **)&skey, (n + 2) * 8));
-    IB_HIP(hipMalloc((void **)&opos, (n + 1) * 4));
-    IB_HIP(hipMalloc((void **)&b.pos, (n + 1) * 4));
-    hipLaunchKernelGGL(k_ib_scatter, dim3(ib_grid(ntup, cap)), dim3(256), 0, 0, flag, slot, key64, ntup, okey, opos);
-    IB_HIP(hipGetLastError());
-    {
-      const unsigned end_bit = (unsigned)(32 + b.nbits_key);
-      IB_TMP(rocprim::radix_sort_pairs(nullptr, need, okey, skey, opos, b.pos, (size_t)n, 0u, end_bit, 0),
-             rocprim::radix_sort_pairs(tmp, need, okey, skey, opos, b.pos, (size_t)n, 0u, end_bit, 0));
+    SMG_HIP(okey.alloc(n + 1)); SMG_HIP(skey.alloc(n + 2));
+    SMG_HIP(opos.alloc(n + 1)); SMG_HIP(b.pos.alloc(n + 1));
+    hipLaunchKernelGGL(k_ib_scatter, dim3(ib_grid(ntup, cap)), dim3(256), 0, 0, flag.get(), slot.get(), key64.get(), ntup, okey.get(), opos.get());
+    SMG_HIP(hipGetLastError());
+    const unsigned end_bit = (unsigned)(32 + b.nbits_key);
+    IB_TMP(rocprim::radix_sort_pairs(nullptr, need, okey.get(), skey.get(), opos.get(), b.pos.get(), (size_t)n, 0u, end_bit, 0),
+           rocprim::radix_sort_pairs(tmp.get(), need, okey.get(), skey.get(), opos.get(), b.pos.get(), (size_t)n, 0u, end_bit, 0));
+    SMG_HIP(head.alloc(n + 1));
+    hipLaunchKernelGGL(k_ib_heads, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey.get(), n, head.get());
+    SMG_HIP(hipGetLastError());
+    IB_TMP(rocprim::exclusive_scan(nullptr, need, head.get(), slot.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), 0),
+           rocprim::exclusive_scan(tmp.get(), need, head.get(), slot.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), 0));
+    if (n) {
+      SMG_HIP(hipMemcpy(&ls, slot + (n - 1), 4, hipMemcpyDeviceToHost));
+      SMG_HIP(hipMemcpy(&lh, head + (n - 1), 4, hipMemcpyDeviceToHost));
     }
-    {
-      uint32_t lh = 0, ls = 0;
-      IB_HIP(hipMalloc((void **)&head, (n + 1) * 4));
-      hipLaunchKernelGGL(k_ib_heads, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey, n, head);
-      IB_HIP(hipGetLastError());
-      IB_TMP(rocprim::exclusive_scan(nullptr, need, head, slot, 0u, (size_t)n, rocprim::plus<uint32_t>(), 0),
-             rocprim::exclusive_scan(tmp, need, head, slot, 0u, (size_t)n, rocprim::plus<uint32_t>(), 0));
-      if (n) {
-        IB_HIP(hipMemcpy(&ls, slot + (n - 1), 4, hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(&lh, head + (n - 1), 4, hipMemcpyDeviceToHost));
-      }
-      b.nwords = ls + lh;
-      IB_HIP(hipMalloc((void **)&b.wordidx, ((size_t)b.nwords + 2) * 4));
-      IB_HIP(hipMalloc((void **)&b.posidx, ((size_t)b.nwords + 2) * 4));
-      IB_HIP(hipMemsetAsync(b.wordidx, 0, ((size_t)b.nwords + 2) * 4, 0));
-      IB_HIP(hipMemsetAsync(b.posidx, 0, ((size_t)b.nwords + 2) * 4, 0));
-      hipLaunchKernelGGL(k_ib_words, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey, head, slot, n, b.wordidx, b.posidx, b.idx);
-      IB_HIP(hipGetLastError());
-      IB_HIP(hipMemcpyAsync(b.posidx + b.nwords, &b.npos, 4, hipMemcpyHostToDevice, 0));       // posidx[nwords] = npos
-    }
+    b.nwords = ls + lh;
+    SMG_HIP(b.wordidx.alloc((size_t)b.nwords + 2)); SMG_HIP(b.posidx.alloc((size_t)b.nwords + 2));
+    SMG_HIP(hipMemsetAsync(b.wordidx, 0, ((size_t)b.nwords + 2) * 4, 0)); SMG_HIP(hipMemsetAsync(b.posidx, 0, ((size_t)b.nwords + 2) * 4, 0));
+    hipLaunchKernelGGL(k_ib_words, dim3(ib_grid(n, cap)), dim3(256), 0, 0, skey.get(), head.get(), slot.get(), n, b.wordidx.get(), b.posidx.get(), b.idx.get());
+    SMG_HIP(hipGetLastError());
+    SMG_HIP(hipMemcpyAsync(b.posidx + b.nwords, &b.npos, 4, hipMemcpyHostToDevice, 0));       // posidx[nwords] = npos
   }
   // run ends -> prefix sums: keys without elements take the count of their predecessor (running maximum)
-  IB_TMP(rocprim::inclusive_scan(nullptr, need, b.idx, b.idx, (size_t)b.nkeys + 1, rocprim::maximum<uint32_t>(), 0),
-         rocprim::inclusive_scan(tmp, need, b.idx, b.idx, (size_t)b.nkeys + 1, rocprim::maximum<uint32_t>(), 0));
-  IB_HIP(hipEventRecord(e1, 0));
-  IB_HIP(hipEventSynchronize(e1));
-  IB_HIP(hipEventElapsedTime(&b.build_ms, e0, e1));
+  IB_TMP(rocprim::inclusive_scan(nullptr, need, b.idx.get(), b.idx.get(), (size_t)b.nkeys + 1, rocprim::maximum<uint32_t>(), 0),
+         rocprim::inclusive_scan(tmp.get(), need, b.idx.get(), b.idx.get(), (size_t)b.nkeys + 1, rocprim::maximum<uint32_t>(), 0));
+  SMG_HIP(hipEventRecord(e1, 0));
+  SMG_HIP(hipEventSynchronize(e1));
+  SMG_HIP(hipEventElapsedTime(&b.build_ms, e0, e1));
 #undef IB_TMP
-  }
-  (void)hipFree(d_sop); (void)hipFree(flag); (void)hipFree(slot); (void)hipFree(key64); (void)hipFree(okey); (void)hipFree(skey);
-  (void)hipFree(opos); (void)hipFree(head); (void)hipFree(tmp); (void)hipFree(key32); (void)hipFree(skey32); (void)hipFree(d_nvalid);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *out = b;
+  *out = std::move(b);
   return 0;
-fail:
-  (void)hipFree(d_sop); (void)hipFree(flag); (void)hipFree(slot); (void)hipFree(key64); (void)hipFree(okey); (void)hipFree(skey);
-  (void)hipFree(opos); (void)hipFree(head); (void)hipFree(tmp); (void)hipFree(key32); (void)hipFree(skey32); (void)hipFree(d_nvalid);
-  (void)hipFree(b.packed); (void)hipFree(b.pos); (void)hipFree(b.idx); (void)hipFree(b.wordidx); (void)hipFree(b.posidx);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return -1;
 }
 
 }  // namespace smg

@@ -17,7 +17,9 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "../../include/smaltgpu.h"
+#include "smg_devmem.hpp"
 #include "smg_reads_dev.hpp"
+#include "smg_text.hpp"
 
 extern "C" int smaltgpu_set_error(int code, const char *msg);   // smaltgpu.cpp
 
@@ -50,41 +52,26 @@ __global__ void __launch_bounds__(256) k_rd_mark(const uint32_t *jump, uint8_t *
   }
 }
 
-// inclusive sums of a and b over the workgroup's 256 threads (LDS: 2 x 256 x 8 bytes)
-__device__ inline void rd_block_scan(uint64_t &a, uint64_t &b, uint64_t (*sh)[256]) {
-  __syncthreads();                      // the last use of sh is over
-  sh[0][threadIdx.x] = a; sh[1][threadIdx.x] = b;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    uint64_t xa = 0, xb = 0;
-    if (threadIdx.x >= d) { xa = sh[0][threadIdx.x - d]; xb = sh[1][threadIdx.x - d]; }
-    __syncthreads();
-    a += xa; b += xb;
-    sh[0][threadIdx.x] = a; sh[1][threadIdx.x] = b;
-    __syncthreads();
-  }
-}
-
 __global__ void __launch_bounds__(256) k_rd_sums(const RdStep *step, const uint8_t *mark, uint64_t nn, uint64_t ntile, int is_last, uint64_t *part_c, uint64_t *part_b,
                                                  RdSum *sum) {
-  __shared__ uint64_t sh[2][256];
+  __shared__ TxPair wsum[4];
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const uint64_t v = tile * RD_NODE_TILE + threadIdx.x;
-    uint64_t c = 0, b = 0;
+    TxPair x = {0, 0}, tot;                                                    // records, bases
     if (v < nn && mark[v]) {
       const uint32_t kf = step[v].kf;
-      if (rd_is_record(kf)) { c = 1; b = step[v].n; }
+      if (rd_is_record(kf)) { x.a = 1; x.b = step[v].n; }
       if (rd_stops(kf, is_last != 0)) atomicMin(&sum->stop_node, (uint32_t)v);
     }
-    rd_block_scan(c, b, sh);
-    if (threadIdx.x == 255) { part_c[tile] = c; part_b[tile] = b; }
+    tx_block_scan_sum(x, wsum, &tot);
+    if (threadIdx.x == 0) { part_c[tile] = tot.a; part_b[tile] = tot.b; }
   }
 }
 
 // rec, read_off, hdr_off: room for nn records (read_off: nn + 1); read_off[0] is set by the caller
 __global__ void __launch_bounds__(256) k_rd_number(const RdStep *step, const uint8_t *mark, uint64_t nn, uint64_t ntile, uint32_t max_reads, const uint64_t *part_c,
                                                    const uint64_t *part_b, RdSum *sum, RdRec *rec, uint64_t *read_off, uint64_t *hdr_off) {
-  __shared__ uint64_t sh[2][256];
+  __shared__ TxPair wsum[4];
   const uint32_t stop_node = sum->stop_node;                                   // k_rd_sums is over
   for (uint64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const uint64_t v = tile * RD_NODE_TILE + threadIdx.x;
@@ -93,9 +80,9 @@ __global__ void __launch_bounds__(256) k_rd_number(const RdStep *step, const uin
     s.kf = RD_DROP; s.n = 0;
     if (marked) s = step[v];
     const bool r = marked && rd_is_record(s.kf);
-    uint64_t c = r ? 1 : 0, b = r ? s.n : 0;
-    rd_block_scan(c, b, sh);
-    const uint64_t idx = part_c[tile] + c - (r ? 1 : 0), off = part_b[tile] + b - (r ? s.n : 0);
+    TxPair tot;
+    const TxPair pre = tx_block_scan_sum(TxPair{r ? 1u : 0u, r ? s.n : 0}, wsum, &tot);       // the tile's records and bases in front of the node
+    const uint64_t idx = part_c[tile] + pre.a, off = part_b[tile] + pre.b;
     if (marked && v == stop_node) { sum->stop_kf = s.kf; sum->stop_idx = idx; sum->stop_hdr_off = s.hdr_off; }
     if (rd_taken(s.kf, marked, v, idx, stop_node, max_reads) && idx < nn) {
       rec[idx] = rd_record(s, off); read_off[idx + 1] = off + s.n; hdr_off[idx] = s.hdr_off;
@@ -108,14 +95,14 @@ __global__ void __launch_bounds__(256) k_rd_number(const RdStep *step, const uin
 __global__ void __launch_bounds__(256) k_rd_emit(const uint8_t *text, uint64_t len, uint32_t block_bytes, const uint64_t *blk_nb, const RdRec *rec, uint64_t nrec,
                                                  uint8_t *bases, uint8_t *quals, uint64_t total) {
   __shared__ uint32_t wsum[4];
-  const uint64_t b0 = (uint64_t)blockIdx.x * block_bytes, b1 = len - b0 < block_bytes ? len : b0 + block_bytes;
+  const auto [b0, b1] = tx_block_range(len, block_bytes);
   uint64_t run_nb = blk_nb[blockIdx.x];                                        // the non-blank bytes in front of the tile; the same in every thread
   for (uint64_t t0 = b0; t0 < b1; t0 += FA_TILE) {
-    uint8_t c[FA_LANE_BYTES], prev;
+    uint8_t c[FA_LANE_BYTES];
     uint64_t o;
-    const uint32_t n = fq_lane_load(text, t0, b1, &o, c, &prev);
+    const uint32_t n = tx_lane_load(text, t0, b1, &o, c);
     uint32_t tot;
-    const uint32_t pre = fq_block_scan_sum(fq_lane_counts(c, n, 0) & 0xFFFFu, wsum, &tot);
+    const uint32_t pre = tx_block_scan_sum(fq_lane_counts(c, n, 0) & 0xFFFFu, wsum, &tot);
     rd_emit_lane(c, n, o, run_nb + pre, rec, nrec, bases, quals, total);
     run_nb += tot;
   }
@@ -126,30 +113,15 @@ __global__ void __launch_bounds__(256) k_rd_emit(const uint8_t *text, uint64_t l
 using namespace smg;
 
 // ---- the handle ------------------------------------------------------------------------------------------------------------
-namespace {
-struct DevBuf {                          // a device allocation that only grows
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t need(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-}  // namespace
-
 struct smaltgpu_reads_dev {
   int device = 0;
   hipStream_t stream = nullptr;
   uint32_t block_bytes = RD_BLOCK_DEFAULT, max_groups = RD_GROUPS_DEFAULT, guard = 0;
-  // scratch, sized from len and ncand
-  DevBuf text, gran, blk_nb, blk_cd, cand, step, jump, mark, part_c, part_b, rec, hdr, sum;
+  // scratch, sized from len and ncand; every allocation only grows (DevMem::need) and goes with the handle
+  DevMem<uint8_t> text, mark; DevMem<uint32_t> gran, jump; DevMem<uint64_t> blk_nb, blk_cd, cand, part_c, part_b, hdr;
+  DevMem<RdStep> step; DevMem<RdRec> rec; DevMem<RdSum> sum;
   // the device view
-  DevBuf bases, quals, read_off;
+  DevMem<uint8_t> bases, quals; DevMem<uint64_t> read_off;
   size_t exact[3] = {0, 0, 0};           // bytes of the three arrays of the last parse (the guard lies behind them)
   // the host view
   std::vector<uint8_t> h_bases, h_quals;
@@ -158,7 +130,7 @@ struct smaltgpu_reads_dev {
   uint32_t launches = 0;
 };
 
-#define RD_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof(b_), "%s: %s", #x, hipGetErrorString(e_)); \
+#define RD_HIP(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; hip_error_text(b_, sizeof(b_), #x, e_); \
                        return smaltgpu_set_error(e_ == hipErrorOutOfMemory ? SMALTGPU_ENOMEM : SMALTGPU_ENODEV, b_); } } while (0)
 
 extern "C" smaltgpu_reads_dev *smaltgpu_reads_dev_create(int device) {
@@ -179,8 +151,6 @@ extern "C" void smaltgpu_reads_dev_free(smaltgpu_reads_dev *h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-  for (DevBuf *b : {&h->text, &h->gran, &h->blk_nb, &h->blk_cd, &h->cand, &h->step, &h->jump, &h->mark, &h->part_c, &h->part_b, &h->rec, &h->hdr, &h->sum, &h->bases,
-                    &h->quals, &h->read_off}) b->release();
   delete h;
 }
 
@@ -195,21 +165,22 @@ extern "C" int smaltgpu_reads_dev_configure(smaltgpu_reads_dev *h, uint32_t bloc
 
 extern "C" int smaltgpu_reads_dev_readback(smaltgpu_reads_dev *h, int which, void *dst, uint64_t cap, uint64_t *nbytes, uint32_t *launches) {
   if (!h || which < 0 || which > 2 || !dst || !nbytes) return smaltgpu_set_error(SMALTGPU_EARG, "bad argument");
-  DevBuf *b = which == 0 ? &h->bases : which == 1 ? &h->quals : &h->read_off;
+  const void *src[3] = {h->bases.get(), h->quals.get(), h->read_off.get()};
+  const size_t held[3] = {h->bases.bytes(), h->quals.bytes(), h->read_off.bytes()};
   const uint64_t n = h->exact[which] + h->guard;
   if (launches) *launches = h->launches;
   *nbytes = h->exact[which];
-  if (!b->p || n > b->cap || n > cap) return smaltgpu_set_error(SMALTGPU_EARG, "nothing to read back, or no room for it");
+  if (!src[which] || n > held[which] || n > cap) return smaltgpu_set_error(SMALTGPU_EARG, "nothing to read back, or no room for it");
   RD_HIP(hipSetDevice(h->device));
   RD_HIP(hipStreamSynchronize(h->stream));
-  RD_HIP(hipMemcpy(dst, b->p, n, hipMemcpyDeviceToHost));
+  RD_HIP(hipMemcpy(dst, src[which], n, hipMemcpyDeviceToHost));
   return SMALTGPU_OK;
 }
 
 static int rd_fill_views(smaltgpu_reads_dev *h, uint64_t len, int is_last, uint32_t max_reads, uint64_t nreads, uint64_t total, bool has_qual, uint64_t rec_end,
                          const char *text, smaltgpu_reads_view *hv, smaltgpu_reads_device_view *dv) {
   if (dv) {
-    dv->d_bases = (const uint8_t *)h->bases.p; dv->d_quals = has_qual ? (const uint8_t *)h->quals.p : nullptr; dv->d_read_off = (const uint64_t *)h->read_off.p;
+    dv->d_bases = h->bases.get(); dv->d_quals = has_qual ? h->quals.get() : nullptr; dv->d_read_off = h->read_off.get();
     dv->nreads = (uint32_t)nreads; dv->has_qual = has_qual ? 1u : 0u; dv->total_bases = total;
     dv->consumed = rd_consumed(len, is_last != 0, max_reads, nreads, rec_end);
   }
@@ -236,63 +207,63 @@ extern "C" int smaltgpu_reads_parse_device(smaltgpu_reads_dev *h, const char *te
   if (dv) memset(dv, 0, sizeof(*dv));
   RD_HIP(hipSetDevice(h->device));
   hipStream_t st = h->stream;
-  uint32_t block = h->block_bytes;
-  while ((len + block - 1) / block > (1ull << 20) && block < FA_BLOCK_MAX) block *= 2;
-  const uint64_t nblk = (len + block - 1) / block, padded = (len + FA_TILE - 1) / FA_TILE * FA_TILE;
-  if (nblk > 0x7fffffffull) return smaltgpu_set_error(SMALTGPU_EARG, "the text is too long for one call");
+  TextBlocks g;
+  if (!text_blocks(len, h->block_bytes, &g)) return smaltgpu_set_error(SMALTGPU_EARG, "the text is too long for one call");
+  const uint32_t block = g.block_bytes;
+  const uint64_t nblk = g.nblk, padded = g.padded;
   h->launches = 0;
   h->h_bases.assign(1, 0); h->h_quals.clear(); h->h_off.assign(1, 0); h->h_hdr.clear();
   h->exact[0] = h->exact[1] = 0; h->exact[2] = sizeof(uint64_t);
   const uint64_t zero = 0;
   if (!len) {                            // as the host parser: no reads, nothing consumed
-    RD_HIP(h->bases.need(1 + h->guard)); RD_HIP(h->quals.need(1 + h->guard)); RD_HIP(h->read_off.need(sizeof(uint64_t) + h->guard));
-    if (h->guard) { RD_HIP(hipMemsetAsync(h->bases.p, 0xA5, h->guard, st)); RD_HIP(hipMemsetAsync(h->quals.p, 0xA5, h->guard, st)); RD_HIP(hipMemsetAsync(h->read_off.p, 0xA5, 8 + h->guard, st)); }
-    RD_HIP(hipMemcpyAsync(h->read_off.p, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+    RD_HIP(h->bases.need(1 + h->guard)); RD_HIP(h->quals.need(1 + h->guard)); RD_HIP(h->read_off.need(1 + (h->guard + 7) / 8));
+    if (h->guard) { RD_HIP(hipMemsetAsync(h->bases.get(), 0xA5, h->guard, st)); RD_HIP(hipMemsetAsync(h->quals.get(), 0xA5, h->guard, st)); RD_HIP(hipMemsetAsync(h->read_off.get(), 0xA5, 8 + h->guard, st)); }
+    RD_HIP(hipMemcpyAsync(h->read_off.get(), &zero, sizeof(zero), hipMemcpyHostToDevice, st));
     RD_HIP(hipStreamSynchronize(st));
     return rd_fill_views(h, 0, is_last, max_reads, 0, 0, false, 0, text, hv, dv);
   }
   // candidates and prefix counts
   RD_HIP(h->text.need(padded));
-  RD_HIP(h->gran.need(padded / FQ_GRAN * sizeof(uint32_t)));
-  RD_HIP(h->blk_nb.need((nblk + 1) * sizeof(uint64_t)));
-  RD_HIP(h->blk_cd.need((nblk + 1) * sizeof(uint64_t)));
-  RD_HIP(h->sum.need(sizeof(RdSum)));
-  RD_HIP(hipMemcpyAsync(h->text.p, text, len, hipMemcpyHostToDevice, st));
-  RD_HIP(fq_launch_counts(st, (const uint8_t *)h->text.p, len, block, nblk, (uint32_t *)h->gran.p, (uint64_t *)h->blk_nb.p, (uint64_t *)h->blk_cd.p));
+  RD_HIP(h->gran.need(padded / FQ_GRAN));
+  RD_HIP(h->blk_nb.need(nblk + 1));
+  RD_HIP(h->blk_cd.need(nblk + 1));
+  RD_HIP(h->sum.need(1));
+  RD_HIP(hipMemcpyAsync(h->text.get(), text, len, hipMemcpyHostToDevice, st));
+  RD_HIP(fq_launch_counts(st, h->text.get(), len, block, nblk, h->gran.get(), h->blk_nb.get(), h->blk_cd.get()));
   h->launches += 2;
   uint64_t tot[2] = {0, 0};
-  RD_HIP(hipMemcpyAsync(&tot[0], (uint64_t *)h->blk_nb.p + nblk, 8, hipMemcpyDeviceToHost, st));
-  RD_HIP(hipMemcpyAsync(&tot[1], (uint64_t *)h->blk_cd.p + nblk, 8, hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(&tot[0], h->blk_nb + nblk, 8, hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(&tot[1], h->blk_cd + nblk, 8, hipMemcpyDeviceToHost, st));
   RD_HIP(hipStreamSynchronize(st));
   if (tot[0] > len || tot[1] > len) return smaltgpu_set_error(SMALTGPU_EINTERNAL, "the counts of the text exceed its length");
   const uint64_t ncand = tot[1], nn = ncand + 1, ntile = (nn + RD_NODE_TILE - 1) / RD_NODE_TILE;
   if (nn >= 0x7fffffffull) return smaltgpu_set_error(SMALTGPU_EARG, "the text holds too many prompts for one call");
   const uint32_t L = rd_levels(nn), ntab = L ? L : 1;
-  RD_HIP(h->cand.need((ncand + 1) * sizeof(uint64_t)));
-  RD_HIP(h->step.need(nn * sizeof(RdStep)));
-  RD_HIP(h->jump.need((size_t)ntab * (nn + 1) * sizeof(uint32_t)));
+  RD_HIP(h->cand.need(ncand + 1));
+  RD_HIP(h->step.need(nn));
+  RD_HIP(h->jump.need((size_t)ntab * (nn + 1)));
   RD_HIP(h->mark.need(nn + 1));
-  RD_HIP(h->part_c.need((ntile + 1) * sizeof(uint64_t)));
-  RD_HIP(h->part_b.need((ntile + 1) * sizeof(uint64_t)));
-  RD_HIP(h->rec.need(nn * sizeof(RdRec)));
-  RD_HIP(h->hdr.need(nn * sizeof(uint64_t)));
+  RD_HIP(h->part_c.need(ntile + 1));
+  RD_HIP(h->part_b.need(ntile + 1));
+  RD_HIP(h->rec.need(nn));
+  RD_HIP(h->hdr.need(nn));
   // the device view: no more bases than non-blank bytes, no more reads than nodes
   const size_t off_bytes = (size_t)(nn + 1) * sizeof(uint64_t);
-  RD_HIP(h->bases.need((size_t)tot[0] + 1 + h->guard)); RD_HIP(h->quals.need((size_t)tot[0] + 1 + h->guard)); RD_HIP(h->read_off.need(off_bytes + h->guard));
+  RD_HIP(h->bases.need((size_t)tot[0] + 1 + h->guard)); RD_HIP(h->quals.need((size_t)tot[0] + 1 + h->guard)); RD_HIP(h->read_off.need(nn + 1 + (h->guard + 7) / 8));
   if (h->guard) {                        // tests: the pattern lies everywhere, so whatever is written behind an array shows
-    RD_HIP(hipMemsetAsync(h->bases.p, 0xA5, (size_t)tot[0] + 1 + h->guard, st)); RD_HIP(hipMemsetAsync(h->quals.p, 0xA5, (size_t)tot[0] + 1 + h->guard, st));
-    RD_HIP(hipMemsetAsync(h->read_off.p, 0xA5, off_bytes + h->guard, st));
+    RD_HIP(hipMemsetAsync(h->bases.get(), 0xA5, (size_t)tot[0] + 1 + h->guard, st)); RD_HIP(hipMemsetAsync(h->quals.get(), 0xA5, (size_t)tot[0] + 1 + h->guard, st));
+    RD_HIP(hipMemsetAsync(h->read_off.get(), 0xA5, off_bytes + h->guard, st));
   }
-  if (ncand) { RD_HIP(fq_launch_cands(st, (const uint8_t *)h->text.p, len, block, nblk, (const uint64_t *)h->blk_cd.p, (uint64_t *)h->cand.p, ncand)); h->launches++; }
+  if (ncand) { RD_HIP(fq_launch_cands(st, h->text.get(), len, block, nblk, h->blk_cd.get(), h->cand.get(), ncand)); h->launches++; }
   FqText t;
-  t.text = (const uint8_t *)h->text.p; t.len = len; t.block_bytes = block; t.pad = 0; t.blk_nb = (const uint64_t *)h->blk_nb.p; t.gran_nb = (const uint32_t *)h->gran.p;
-  t.cand = (const uint64_t *)h->cand.p; t.ncand = ncand; t.nblk = nblk;
+  t.text = h->text.get(); t.len = len; t.block_bytes = block; t.pad = 0; t.blk_nb = h->blk_nb.get(); t.gran_nb = h->gran.get();
+  t.cand = h->cand.get(); t.ncand = ncand; t.nblk = nblk;
   const uint64_t G = h->max_groups;
   const unsigned g_wave = (unsigned)((nn + 3) / 4 < G ? (nn + 3) / 4 : G), g_node = (unsigned)((nn + 1 + 255) / 256 < G ? (nn + 1 + 255) / 256 : G),
                  g_tile = (unsigned)(ntile < G ? ntile : G);
-  uint32_t *jump = (uint32_t *)h->jump.p;
-  uint8_t *mark = (uint8_t *)h->mark.p;
-  RdSum *sum = (RdSum *)h->sum.p;
+  uint32_t *jump = h->jump.get();
+  uint8_t *mark = h->mark.get();
+  RdSum *sum = h->sum.get();
   RdSum s0;
   memset(&s0, 0, sizeof(s0));
   s0.stop_node = RD_NONE;
@@ -300,8 +271,8 @@ extern "C" int smaltgpu_reads_parse_device(smaltgpu_reads_dev *h, const char *te
   RD_HIP(hipMemsetAsync(mark, 0, nn + 1, st));
   RD_HIP(hipMemcpyAsync(mark, &one, 1, hipMemcpyHostToDevice, st));
   RD_HIP(hipMemcpyAsync(sum, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
-  RD_HIP(hipMemcpyAsync(h->read_off.p, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_rd_step, dim3(g_wave), dim3(256), 0, st, t, nn, (RdStep *)h->step.p, jump);
+  RD_HIP(hipMemcpyAsync(h->read_off.get(), &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_rd_step, dim3(g_wave), dim3(256), 0, st, t, nn, h->step.get(), jump);
   RD_HIP(hipGetLastError()); h->launches++;
   for (uint32_t r = 1; r < L; r++) {
     hipLaunchKernelGGL(k_rd_double, dim3(g_node), dim3(256), 0, st, jump + (size_t)(r - 1) * (nn + 1), jump + (size_t)r * (nn + 1), nn + 1);
@@ -311,12 +282,12 @@ extern "C" int smaltgpu_reads_parse_device(smaltgpu_reads_dev *h, const char *te
     hipLaunchKernelGGL(k_rd_mark, dim3(g_node), dim3(256), 0, st, jump + (size_t)r * (nn + 1), mark, nn);
     RD_HIP(hipGetLastError()); h->launches++;
   }
-  hipLaunchKernelGGL(k_rd_sums, dim3(g_tile), dim3(256), 0, st, (const RdStep *)h->step.p, mark, nn, ntile, is_last, (uint64_t *)h->part_c.p, (uint64_t *)h->part_b.p, sum);
+  hipLaunchKernelGGL(k_rd_sums, dim3(g_tile), dim3(256), 0, st, h->step.get(), mark, nn, ntile, is_last, h->part_c.get(), h->part_b.get(), sum);
   RD_HIP(hipGetLastError()); h->launches++;
-  RD_HIP(fq_launch_scan(st, (uint64_t *)h->part_c.p, (uint64_t *)h->part_b.p, ntile));
+  RD_HIP(fq_launch_scan(st, h->part_c.get(), h->part_b.get(), ntile));
   h->launches++;
-  hipLaunchKernelGGL(k_rd_number, dim3(g_tile), dim3(256), 0, st, (const RdStep *)h->step.p, mark, nn, ntile, max_reads, (const uint64_t *)h->part_c.p,
-                     (const uint64_t *)h->part_b.p, sum, (RdRec *)h->rec.p, (uint64_t *)h->read_off.p, (uint64_t *)h->hdr.p);
+  hipLaunchKernelGGL(k_rd_number, dim3(g_tile), dim3(256), 0, st, h->step.get(), mark, nn, ntile, max_reads, h->part_c.get(),
+                     h->part_b.get(), sum, h->rec.get(), h->read_off.get(), h->hdr.get());
   RD_HIP(hipGetLastError()); h->launches++;
   RdSum hs;
   RD_HIP(hipMemcpyAsync(&hs, sum, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -329,23 +300,23 @@ extern "C" int smaltgpu_reads_parse_device(smaltgpu_reads_dev *h, const char *te
   uint64_t total = 0, rec_end = 0;
   if (nreads) {
     RdRec last;
-    RD_HIP(hipMemcpyAsync(&total, (uint64_t *)h->read_off.p + nreads, 8, hipMemcpyDeviceToHost, st));
-    RD_HIP(hipMemcpyAsync(&last, (RdRec *)h->rec.p + (nreads - 1), sizeof(last), hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpyAsync(&total, h->read_off + nreads, 8, hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpyAsync(&last, h->rec + (nreads - 1), sizeof(last), hipMemcpyDeviceToHost, st));
     RD_HIP(hipStreamSynchronize(st));
     if (total > tot[0] || last.q1 > len) return smaltgpu_set_error(SMALTGPU_EINTERNAL, "the numbering disagrees with the counts of the text");
     rec_end = last.q1;
-    hipLaunchKernelGGL(k_rd_emit, dim3((unsigned)nblk), dim3(256), 0, st, (const uint8_t *)h->text.p, len, block, (const uint64_t *)h->blk_nb.p, (const RdRec *)h->rec.p,
-                       nreads, (uint8_t *)h->bases.p, has_qual ? (uint8_t *)h->quals.p : nullptr, total);
+    hipLaunchKernelGGL(k_rd_emit, dim3((unsigned)nblk), dim3(256), 0, st, h->text.get(), len, block, h->blk_nb.get(), h->rec.get(),
+                       nreads, h->bases.get(), has_qual ? h->quals.get() : nullptr, total);
     RD_HIP(hipGetLastError()); h->launches++;
   }
   h->exact[0] = (size_t)total; h->exact[1] = has_qual ? (size_t)total : 0; h->exact[2] = (size_t)(nreads + 1) * sizeof(uint64_t);
   if (hv) {                              // the compacted arrays, and the header offsets for the names
     h->h_bases.resize(total ? total : 1); h->h_off.resize(nreads + 1); h->h_hdr.resize(nreads);
     if (has_qual) h->h_quals.resize(total ? total : 1);
-    if (total) RD_HIP(hipMemcpyAsync(h->h_bases.data(), h->bases.p, total, hipMemcpyDeviceToHost, st));
-    if (total && has_qual) RD_HIP(hipMemcpyAsync(h->h_quals.data(), h->quals.p, total, hipMemcpyDeviceToHost, st));
-    RD_HIP(hipMemcpyAsync(h->h_off.data(), h->read_off.p, (nreads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (nreads) RD_HIP(hipMemcpyAsync(h->h_hdr.data(), h->hdr.p, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (total) RD_HIP(hipMemcpyAsync(h->h_bases.data(), h->bases.get(), total, hipMemcpyDeviceToHost, st));
+    if (total && has_qual) RD_HIP(hipMemcpyAsync(h->h_quals.data(), h->quals.get(), total, hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpyAsync(h->h_off.data(), h->read_off.get(), (nreads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (nreads) RD_HIP(hipMemcpyAsync(h->h_hdr.data(), h->hdr.get(), nreads * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   }
   RD_HIP(hipStreamSynchronize(st));
   if (hv) for (uint64_t i = 0; i < nreads; i++) if (h->h_hdr[i] >= len) return smaltgpu_set_error(SMALTGPU_EINTERNAL, "a header offset lies behind the text");

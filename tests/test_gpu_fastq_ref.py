@@ -97,6 +97,32 @@ def test_a_refusal_names_the_record_its_prompt_and_its_offset(monkeypatch):
     assert "'s3'" in msg and "prompt 5 " in msg and "byte %d)" % text.index(b"@s3\n") in msg and "397 characters for 401 bases" in msg, msg
 
 
+def test_a_text_handed_over_by_the_fasta_route_is_refused_and_the_next_one_read(monkeypatch):
+    """the text begins with a '>' record, so the FASTA route runs first, finds the '@' and leaves the text in HBM for the walk over
+    the records; the walk refuses the last record, whose quality line is one character short.  The next call in the same process,
+    on the text with the quality repaired, goes the same way and is read."""
+    import re
+    import numpy as np
+    from smalt_amd import api
+    _set_block(monkeypatch, "64")
+    rng = np.random.default_rng(99)
+    head = b">fa one\n" + fq._rand(rng, 70) + b"\n" + fq._rand(rng, 45) + b"\n@s2 x\n" + fq._rand(rng, 90) + b"\n+\n" + fq._rand(rng, 90, fq.QUAL[1:30]) + b"\n"
+    seq3, qual3 = fq._rand(rng, 130), fq._rand(rng, 130, fq.QUAL[1:30])
+    bad, good = head + b"@s3\n" + seq3 + b"\n+\n" + qual3[:-1] + b"\n", head + b"@s3\n" + seq3 + b"\n+\n" + qual3 + b"\n"
+    assert len(good) < 1000 and len(bad) > 5 * 64
+    with pytest.raises(ValueError) as mi:
+        fq.parse_model_fq(bad)
+    name, m, n = re.fullmatch(re.escape(fq.WRONG) + r": record '(.*)' has (\d+) quality characters for (\d+) bases", str(mi.value)).groups()
+    assert (name, m, n) == ("s3", "129", "130")
+    with pytest.raises(api.SmaltGpuError) as ei:
+        api.parse_fasta(bad, 0, fastq=True)
+    msg = str(ei.value)
+    assert fq.WRONG in msg and "record '%s'" % name in msg and "byte %d)" % bad.index(b"@s3\n") in msg and "%s characters for %s bases" % (m, n) in msg, msg
+    names, seqs = fq.parse_model_fq(good)
+    assert names == ["fa one", "s2 x", "s3"] and [len(s) for s in seqs] == [115, 90, 130]
+    assert api.parse_fasta(good, 0, fastq=True)[:2] == (names, seqs)
+
+
 @pytest.mark.parametrize("block", BLOCKS, ids=["b64", "b256", "default"])
 def test_plain_fasta_texts_give_the_same_files_with_the_flag(block, monkeypatch, tmp_path):
     from smalt_amd import api

@@ -117,6 +117,31 @@ def test_two_parses_on_one_handle(dev):
     assert dev_line(dev, rd.CORPUS["fasta_wrapped"][0]) == rd.host_line(rd.CORPUS["fasta_wrapped"][0])
 
 
+def _short_reads(nrec, drops):
+    """nrec four-line FASTQ records with reads of 1 to 3 bases and no prompt character in a quality: two nodes a record.  drops:
+    a '+' segment behind every record, which the chain of records passes through and drops (three nodes a record)"""
+    out = []
+    for i in range(nrec):
+        n = 1 + i % 3
+        out.append(b"@%x\n%s\n+\n%s\n" % (i, b"ACGTN"[i % 5:i % 5 + 1] * n, b"#5?I"[i % 4:i % 4 + 1] * n))
+        if drops:
+            out.append(b"+%x\nJJ\n" % i)
+    return b"".join(out)
+
+
+@pytest.mark.parametrize("drops", [False, True], ids=["records", "dropped_segments_between"])
+def test_node_counts_at_the_borders_of_the_numbering_scan(drops, dev):
+    """k_rd_sums and k_rd_number number the marked nodes RD_NODE_TILE (256) at a time, 64 to a wave: node counts of 2 and of one
+    below, at and above two and four tiles (three and six with the dropped segments), records on both sides of every wave border"""
+    for nrec in (1, 255, 256, 257, 513):
+        text = _short_reads(nrec, drops)
+        assert len(text) < 16_000
+        want = rd.host_line(text)
+        r = rd.parse_line(want[0])
+        assert r["nreads"] == nrec and r["has_qual"] == 1 and [len(s) for s in r["reads"]] == [1 + i % 3 for i in range(nrec)]
+        assert dev_line(dev, text) == want, (nrec, drops)
+
+
 @pytest.mark.parametrize("groups", [0, 1], ids=["grid", "one_workgroup"])
 def test_deep_chain(groups):
     """70 000 two-base reads whose quality lines begin with '@': three candidates a record, two of them on the chain, which is
